@@ -2,12 +2,19 @@
 
 Driver contract (BASELINE.json): measures tokens/sec (whole node) on the
 Llama-3-8B config with synthetic data and random-init weights.
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 N>1 is launched by the driver via torch.distributed.run (one rank per GPU,
 RCCL); parallelism is data parallel + ZeRO stage-2 sharding (the reference's
 headline "sd8_stage2"-style recipe).
 
 Prints ONE JSON line from rank 0 with the whole-job aggregate.
+
+A plain run sets up, warms up, times the K steps and prints the result line;
+it measures nothing else.  --dump-outputs DIR additionally writes what the
+last timed step returned (loss, and a fixed seeded sample of the logits) as
+DIR/<name>.npy so that two builds can be compared output for output.  --full
+is reserved for extra measurements that take runs of their own; the benchmark
+has none today, so it changes nothing.
 """
 from __future__ import annotations
 
@@ -52,6 +59,32 @@ MODELS = {
 }
 
 
+# --dump-outputs keeps at most this many logits (float32: 16 MB on disk)
+DUMP_SAMPLE_ELEMS = 1 << 22
+
+
+def dump_outputs(out_dir, loss, logits):
+    """Write the last timed step's outputs (what model(**batch) returned to
+    the training loop) as float32 .npy files.  The logits are too large to
+    store whole, so a fixed seeded sample of their elements is written; the
+    sampled flat indices depend only on the logits' shape."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"),
+            loss.detach().float().reshape(1).cpu().numpy())
+    if logits is None:  # fused head+CE path never materializes logits
+        return
+    flat = logits.detach().reshape(-1)
+    n = flat.numel()
+    if n > DUMP_SAMPLE_ELEMS:
+        g = torch.Generator(device="cpu").manual_seed(20240229)
+        idx = torch.randint(0, n, (DUMP_SAMPLE_ELEMS,), generator=g)
+        flat = flat[idx.to(flat.device)]
+    np.save(os.path.join(out_dir, "logits_sample.npy"),
+            flat.float().cpu().numpy())
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
@@ -63,6 +96,11 @@ def main():
     p.add_argument("--accum", type=int, default=1)
     p.add_argument("--recompute", action="store_true")
     p.add_argument("--lr", type=float, default=3e-4)
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="write the last timed step's outputs as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run measurements beyond the headline figure "
+                        "(none exist today)")
     args = p.parse_args()
 
     world_size = int(os.environ.get("WORLD_SIZE", "1"))
@@ -158,6 +196,9 @@ def main():
             "labels": ids[:, 1:].contiguous().to(device),
         })
 
+    last_step = args.warmup + args.steps - 1
+    kept = {}
+
     def one_step(step_idx: int):
         if zero is not None:
             # flat-bucket engine: zero the persistent grad buffers and
@@ -170,8 +211,11 @@ def main():
             if zero is not None and getattr(zero, "_overlap", False) \
                     and a == args.accum - 1:
                 zero.overlap_active = True  # reduce buckets during backward
-            loss, _ = model(**batch)
+            loss, logits = model(**batch)
             (loss / args.accum).backward()
+        if args.dump_outputs and step_idx == last_step:
+            # keep a reference only; sampled and copied after the timed region
+            kept["logits"] = logits
         if zero is not None:
             zero.reduce_gradients_and_step_pre()
         optimizer.step()
@@ -211,6 +255,10 @@ def main():
         batch_size=args.micro_batch * args.accum, recompute=args.recompute,
     )
     mfu = flops_per_step_per_dev * args.steps / elapsed / MI355X_BF16_PEAK_FLOPS * 100
+
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        dump_outputs(args.dump_outputs, loss, kept.get("logits"))
+    kept.clear()
 
     if rank == 0:
         result = {
