@@ -6,21 +6,11 @@
 // numels) into a device metadata buffer; each block grid-strides over one
 // chunk so a single launch covers every parameter.
 #include "common.h"
+#include "launchers.h"
 
 #define ADAMW_BLOCK 256
 #define ADAMW_CHUNK (1 << 20)  // 1M elements per chunk
 #define MAX_TENSORS_PER_LAUNCH 320
-
-struct AdamWChunk {
-    void* param;       // bf16 or fp32
-    const void* grad;  // matches param dtype
-    float* m;
-    float* v;
-    float* master;     // nullptr when param is fp32
-    long long offset;  // element offset of this chunk within the tensor
-    long long n;       // elements in this chunk
-    int is_bf16;
-};
 
 __global__ void adamw_kernel(
     const AdamWChunk* __restrict__ chunks, int n_chunks,

@@ -4,40 +4,7 @@
 #include <ATen/hip/HIPContext.h>
 #include <vector>
 
-// ---- launcher decls (implemented in the .hip files) ----
-void launch_rms_norm_fwd(const void*, const void*, void*, float*, long long, int, float, hipStream_t);
-void launch_rms_norm_bwd(const void*, const void*, const void*, const float*, void*, float*, float*, void*, bool, long long, int, int, hipStream_t);
-void launch_rope(const void*, void*, const float*, const float*, long long, int, int, int, bool, hipStream_t);
-void launch_swiglu_fwd(const void*, void*, long long, int, hipStream_t);
-void launch_swiglu_bwd(const void*, const void*, void*, long long, int, hipStream_t);
-void launch_ce_fwd(const void*, const long long*, float*, float*, long long, int, long long, hipStream_t);
-void launch_ce_bwd(const float*, const void*, const long long*, const float*, void*, long long, int, long long, hipStream_t);
-void launch_mfma_probe(const void*, const void*, float*, hipStream_t);
-void launch_flash_fwd(const void*, const void*, const void*, void*, float*, int, int, int, int, int, int, float, bool, hipStream_t);
-void launch_flash_fwd_variant(const void*, const void*, const void*, void*, float*, int, int, int, int, int, int, float, bool, int, hipStream_t);
-void launch_flash_bwd(const void*, const void*, const void*, const void*, const void*, const float*, float*, void*, void*, void*, int, int, int, int, int, int, float, bool, hipStream_t);
-void launch_flash_bwd_variant(const void*, const void*, const void*, const void*, const void*, const float*, float*, void*, void*, void*, int, int, int, int, int, int, float, bool, int, hipStream_t);
-void launch_flash_fwd_mask(const void*, const void*, const void*, void*, float*, const int*, int, int, int, int, int, int, float, hipStream_t);
-void launch_flash_bwd_mask(const void*, const void*, const void*, const void*, const void*, const float*, float*, void*, void*, void*, const int*, int, int, int, int, int, int, float, hipStream_t);
-
-struct AdamWChunk {
-    void* param;
-    const void* grad;
-    float* m;
-    float* v;
-    float* master;
-    long long offset;
-    long long n;
-    int is_bf16;
-};
-void launch_adamw(const AdamWChunk*, int, float, float, float, float, float, float, float, hipStream_t);
-void launch_paged_decode_attn(const void*, const void*, const void*, const float*, const float*, const int*, const int*, void*, float*, int, int, int, int, int, int, int, float, int, hipStream_t);
-int paged_decode_nsplit(int, int);
-void launch_wint8_gemv(const void*, const void*, const float*, void*, int, int, int, hipStream_t);
-void launch_fp8_rowwise_quant(const void*, void*, float*, long long, int, hipStream_t);
-void launch_skinny_gemm(const void*, const void*, float*, void*, int, int, int, int, hipStream_t);
-int skinny_gemm_ksplit(int, int, int);
-void launch_rope_cache_append(const void*, void*, void*, void*, float*, float*, const int*, const int*, const float*, const float*, int, int, int, int, int, int, int, const int*, int, hipStream_t);
+#include "launchers.h"
 
 #define CHECK_GPU(x) TORCH_CHECK(x.is_cuda(), #x " must be on GPU")
 #define CHECK_CONTIG(x) TORCH_CHECK(x.is_contiguous(), #x " must be contiguous")
@@ -164,19 +131,6 @@ torch::Tensor mfma_probe(torch::Tensor A, torch::Tensor B) {
     return C;
 }
 
-void launch_mfma32_probe(const void*, const void*, float*, hipStream_t);
-void launch_permlane_probe(int*, int*, hipStream_t);
-void launch_repetition_penalty(void*, const long long*, const int*, const float*,
-                               int, long long, int, hipStream_t);
-void launch_topp_sample(const void*, const float*, const float*, const float*,
-                        const long long*, int, const int*, const int*,
-                        long long*, int, long long, hipStream_t);
-void launch_decode_update(long long*, signed char*, const signed char*, long long*,
-                          int*, int*, const long long*, int, int*, const int*,
-                          long long, int, int, hipStream_t);
-void launch_block_step(int*, int*, signed char*, signed char*, int*, int*,
-                       signed char*, int, int, int, hipStream_t);
-
 void apply_repetition_penalty(torch::Tensor logits, torch::Tensor pre_ids,
                               torch::Tensor pre_lens, torch::Tensor rep_pen) {
     CHECK_GPU(logits); CHECK_CONTIG(logits); CHECK_BF16(logits);
@@ -252,60 +206,77 @@ std::vector<torch::Tensor> permlane_probe() {
     return {o0, o1};
 }
 
-std::vector<torch::Tensor> flash_attn_fwd_ex(torch::Tensor q, torch::Tensor k, torch::Tensor v,
-                                             bool causal, int64_t variant) {
-    int B = q.size(0), Sq = q.size(1), Hq = q.size(2), D = q.size(3);
-    int Skv = k.size(1), Hk = k.size(2);
-    auto o = torch::empty_like(q);
-    auto lse = torch::empty({B, Hq, Sq}, q.options().dtype(torch::kFloat32));
-    float scale = 1.0f / std::sqrt((float)D);
-    launch_flash_fwd_variant(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
-                             lse.data_ptr<float>(), B, Sq, Skv, Hq, Hk, D, scale,
-                             causal, (int)variant, cur_stream());
-    return {o, lse};
+// ---------------------------------------------------------------------------
+// flash attention.  Every entry point validates through check_attn_args, so
+// a shape without a kernel is an error before anything is launched.
+// ---------------------------------------------------------------------------
+// q [B,Sq,Hq,D]; k, v [B,Skv,Hk,D]; backward adds dout, o (shaped like q)
+// and lse [B,Hq,Sq] fp32; FlashMask adds startend with B*Skv elements.
+static void check_attn_args(const torch::Tensor& q, const torch::Tensor& k,
+                            const torch::Tensor& v,
+                            const torch::Tensor* dout = nullptr,
+                            const torch::Tensor* o = nullptr,
+                            const torch::Tensor* lse = nullptr,
+                            const torch::Tensor* startend = nullptr) {
+    auto check4d = [](const torch::Tensor& t, const char* name) {
+        TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
+        TORCH_CHECK(t.scalar_type() == torch::kBFloat16, name, " must be bf16");
+        TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+        TORCH_CHECK(t.dim() == 4, name, " must be [B,S,H,D]");
+    };
+    check4d(q, "q");
+    check4d(k, "k");
+    check4d(v, "v");
+    int64_t B = q.size(0), Sq = q.size(1), Hq = q.size(2), D = q.size(3);
+    int64_t Skv = k.size(1), Hk = k.size(2);
+    TORCH_CHECK(D == 128 || D == 64 || D == 32, "head dim must be 32/64/128, got ", D);
+    TORCH_CHECK(k.sizes() == v.sizes(), "k and v shapes must agree");
+    TORCH_CHECK(k.size(0) == B && k.size(3) == D, "k/v must be [B,Skv,Hk,D] matching q");
+    TORCH_CHECK(Hk > 0 && Hq % Hk == 0, "GQA requires Hq % Hk == 0");
+    if (dout) {
+        check4d(*dout, "dout");
+        TORCH_CHECK(dout->sizes() == q.sizes(), "dout must be shaped like q");
+    }
+    if (o) {
+        check4d(*o, "o");
+        TORCH_CHECK(o->sizes() == q.sizes(), "o must be shaped like q");
+    }
+    if (lse) {
+        TORCH_CHECK(lse->is_cuda() && lse->is_contiguous() &&
+                        lse->scalar_type() == torch::kFloat32 &&
+                        lse->sizes() == at::IntArrayRef({B, Hq, Sq}),
+                    "lse must be a contiguous fp32 [B,Hq,Sq] GPU tensor");
+    }
+    if (startend) {
+        TORCH_CHECK(startend->is_cuda(), "startend must be on GPU");
+        TORCH_CHECK(startend->numel() == B * Skv, "startend must be [B, Skv]");
+    }
 }
 
-std::vector<torch::Tensor> flash_attn_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
-                                          bool causal) {
-    CHECK_GPU(q); CHECK_CONTIG(q); CHECK_BF16(q);
-    CHECK_CONTIG(k); CHECK_CONTIG(v);
-    TORCH_CHECK(q.dim() == 4, "q must be [B,S,H,D]");
+std::vector<torch::Tensor> flash_attn_fwd_ex(torch::Tensor q, torch::Tensor k, torch::Tensor v,
+                                             bool causal, bool force_v1) {
+    check_attn_args(q, k, v);
     int B = q.size(0), Sq = q.size(1), Hq = q.size(2), D = q.size(3);
     int Skv = k.size(1), Hk = k.size(2);
-    TORCH_CHECK(D == 128 || D == 64 || D == 32, "head dim must be 32/64/128");
-    TORCH_CHECK(Hq % Hk == 0, "GQA requires Hq % Hk == 0");
     auto o = torch::empty_like(q);
     auto lse = torch::empty({B, Hq, Sq}, q.options().dtype(torch::kFloat32));
     float scale = 1.0f / std::sqrt((float)D);
     launch_flash_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
                      lse.data_ptr<float>(), B, Sq, Skv, Hq, Hk, D, scale, causal,
-                     cur_stream());
+                     force_v1, cur_stream());
     return {o, lse};
+}
+
+std::vector<torch::Tensor> flash_attn_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
+                                          bool causal) {
+    return flash_attn_fwd_ex(q, k, v, causal, /*force_v1=*/false);
 }
 
 std::vector<torch::Tensor> flash_attn_bwd_ex(torch::Tensor dout, torch::Tensor q,
                                              torch::Tensor k, torch::Tensor v,
                                              torch::Tensor o, torch::Tensor lse,
-                                             bool causal, int64_t variant) {
-    int B = q.size(0), Sq = q.size(1), Hq = q.size(2), D = q.size(3);
-    int Skv = k.size(1), Hk = k.size(2);
-    auto dq = torch::empty_like(q);
-    auto dk_h = torch::empty({B, Skv, Hk, D}, k.options());
-    auto dv_h = torch::empty({B, Skv, Hk, D}, v.options());
-    auto delta = torch::empty({B, Hq, Sq}, q.options().dtype(torch::kFloat32));
-    float scale = 1.0f / std::sqrt((float)D);
-    launch_flash_bwd_variant(dout.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(),
-                             o.data_ptr(), lse.data_ptr<float>(), delta.data_ptr<float>(),
-                             dq.data_ptr(), dk_h.data_ptr(), dv_h.data_ptr(),
-                             B, Sq, Skv, Hq, Hk, D, scale, causal, (int)variant, cur_stream());
-    return {dq, dk_h, dv_h};
-}
-
-std::vector<torch::Tensor> flash_attn_bwd(torch::Tensor dout, torch::Tensor q,
-                                          torch::Tensor k, torch::Tensor v,
-                                          torch::Tensor o, torch::Tensor lse,
-                                          bool causal) {
-    CHECK_GPU(dout); CHECK_CONTIG(dout); CHECK_BF16(dout);
+                                             bool causal, bool force_v1) {
+    check_attn_args(q, k, v, &dout, &o, &lse);
     int B = q.size(0), Sq = q.size(1), Hq = q.size(2), D = q.size(3);
     int Skv = k.size(1), Hk = k.size(2);
     auto dq = torch::empty_like(q);
@@ -316,8 +287,15 @@ std::vector<torch::Tensor> flash_attn_bwd(torch::Tensor dout, torch::Tensor q,
     launch_flash_bwd(dout.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(),
                      o.data_ptr(), lse.data_ptr<float>(), delta.data_ptr<float>(),
                      dq.data_ptr(), dk_h.data_ptr(), dv_h.data_ptr(),
-                     B, Sq, Skv, Hq, Hk, D, scale, causal, cur_stream());
+                     B, Sq, Skv, Hq, Hk, D, scale, causal, force_v1, cur_stream());
     return {dq, dk_h, dv_h};
+}
+
+std::vector<torch::Tensor> flash_attn_bwd(torch::Tensor dout, torch::Tensor q,
+                                          torch::Tensor k, torch::Tensor v,
+                                          torch::Tensor o, torch::Tensor lse,
+                                          bool causal) {
+    return flash_attn_bwd_ex(dout, q, k, v, o, lse, causal, /*force_v1=*/false);
 }
 
 // ---------------------------------------------------------------------------
@@ -363,10 +341,9 @@ void fused_adamw(std::vector<torch::Tensor> params, std::vector<torch::Tensor> g
 
 std::vector<torch::Tensor> flashmask_attn_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                                               torch::Tensor startend) {
-    CHECK_GPU(q); CHECK_CONTIG(q); CHECK_BF16(q);
+    check_attn_args(q, k, v, nullptr, nullptr, nullptr, &startend);
     int B = q.size(0), Sq = q.size(1), Hq = q.size(2), D = q.size(3);
     int Skv = k.size(1), Hk = k.size(2);
-    TORCH_CHECK(startend.numel() == (long long)B * Skv, "startend must be [B, Skv]");
     auto se = startend.to(torch::kInt32).contiguous();
     auto o = torch::empty_like(q);
     auto lse = torch::empty({B, Hq, Sq}, q.options().dtype(torch::kFloat32));
@@ -381,6 +358,7 @@ std::vector<torch::Tensor> flashmask_attn_bwd(torch::Tensor dout, torch::Tensor 
                                               torch::Tensor k, torch::Tensor v,
                                               torch::Tensor o, torch::Tensor lse,
                                               torch::Tensor startend) {
+    check_attn_args(q, k, v, &dout, &o, &lse, &startend);
     int B = q.size(0), Sq = q.size(1), Hq = q.size(2), D = q.size(3);
     int Skv = k.size(1), Hk = k.size(2);
     auto se = startend.to(torch::kInt32).contiguous();

@@ -8,6 +8,7 @@
 // fwd:  loss[n] = lse[n] - (logit[n, y_n] - max[n]),  lse = log(sum exp(l - max))
 // bwd:  dlogits[n, v] = dloss[n] * (softmax[n, v] - 1{v == y_n})
 #include "common.h"
+#include "launchers.h"
 
 #define CE_BLOCK 512
 

@@ -20,84 +20,11 @@
 //
 // v1 (flash_attn.hip) staged P^T/dS^T through LDS between every GEMM
 // pair; measured A/B at the bench shape: v1 191 TF/s -> v2 (this file).
-#include "common.h"
+#include "launchers.h"
+#include "mfma.h"
 
 #define FB2_WAVES 8
 #define FB2_BLOCK (FB2_WAVES * 64)
-
-typedef short8v frag8;
-
-static __device__ __forceinline__ f32x16 mfma32b(frag8 a, frag8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-
-static __device__ __forceinline__ int crow32b(int r, int hi) {
-    return (r & 3) + 8 * (r >> 2) + 4 * hi;
-}
-
-template <int LD>
-static __device__ __forceinline__ char* swzb2(ushort_t* base, int row, int col_elem) {
-    return reinterpret_cast<char*>(base) +
-           (((row * LD + col_elem) * 2) ^ ((row & 7) << 4));
-}
-
-static __device__ __forceinline__ unsigned packbf(float a, float b) {
-    return (unsigned)f32_to_bf16(a) | ((unsigned)f32_to_bf16(b) << 16);
-}
-
-// T12: convert one 16-row slice (regs rb..rb+7 of a 32x32 C tile) into the
-// 8 packed bf16 values each lane needs for the transpose-contraction
-// fragment: lane ends up with X[other = hi*8 + j] at its own column.
-static __device__ __forceinline__ frag8 t12_convert(const f32x16& p, int rb) {
-    unsigned w[4];
-    {
-        unsigned lo0 = packbf(p[rb + 0], p[rb + 1]);
-        unsigned hi0 = packbf(p[rb + 4], p[rb + 5]);
-        auto rr = __builtin_amdgcn_permlane32_swap(lo0, hi0, false, false);
-        w[0] = rr[0]; w[2] = rr[1];
-    }
-    {
-        unsigned lo1 = packbf(p[rb + 2], p[rb + 3]);
-        unsigned hi1 = packbf(p[rb + 6], p[rb + 7]);
-        auto rr = __builtin_amdgcn_permlane32_swap(lo1, hi1, false, false);
-        w[1] = rr[0]; w[3] = rr[1];
-    }
-    frag8 f;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        f[j * 2] = (short)(w[j] & 0xffff);
-        f[j * 2 + 1] = (short)(w[j] >> 16);
-    }
-    return f;
-}
-
-// ---------------------------------------------------------------------------
-// delta[b,h,q] = rowsum(dO * O)
-// ---------------------------------------------------------------------------
-template <int D>
-__global__ void flash_bwd2_delta_kernel(
-    const ushort_t* __restrict__ dout, const ushort_t* __restrict__ o,
-    float* __restrict__ delta, int B, int Sq, int Hq) {
-    long long row = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    long long total = (long long)B * Sq * Hq;
-    if (row >= total) return;
-    int lane = threadIdx.x & 63;
-    const ushort_t* dor = dout + row * D;
-    const ushort_t* orow = o + row * D;
-    float acc = 0.f;
-#pragma unroll
-    for (int i = lane * 2; i < D; i += 128) {
-        acc += bf16_to_f32(dor[i]) * bf16_to_f32(orow[i]);
-        acc += bf16_to_f32(dor[i + 1]) * bf16_to_f32(orow[i + 1]);
-    }
-    acc = wave_reduce_sum(acc);
-    if (lane == 0) {
-        long long h = row % Hq;
-        long long bq = row / Hq;
-        long long bb = bq / Sq, qi = bq % Sq;
-        delta[(bb * Hq + h) * Sq + qi] = acc;
-    }
-}
 
 // ---------------------------------------------------------------------------
 // dQ kernel: q stationary (8 waves x 32 q = 256 q rows/block), kv iterated
@@ -209,15 +136,15 @@ __global__ __launch_bounds__(FB2_BLOCK) void flash_bwd2_dq_kernel(
             se_lds[buf][tid] =
                 (g < Skv) ? startend[(long long)b * Skv + g] : 0;
         }
-        *reinterpret_cast<short8v*>(swzb2<D>(k_lds[buf], s_row0, s_col)) = sk0;
-        *reinterpret_cast<short8v*>(swzb2<D>(k_lds[buf], s_row0 + 1, s_col)) = sk1;
-        *reinterpret_cast<short8v*>(swzb2<D>(v_lds[buf], s_row0, s_col)) = sv0;
-        *reinterpret_cast<short8v*>(swzb2<D>(v_lds[buf], s_row0 + 1, s_col)) = sv1;
+        *reinterpret_cast<short8v*>(swz<D>(k_lds[buf], s_row0, s_col)) = sk0;
+        *reinterpret_cast<short8v*>(swz<D>(k_lds[buf], s_row0 + 1, s_col)) = sk1;
+        *reinterpret_cast<short8v*>(swz<D>(v_lds[buf], s_row0, s_col)) = sv0;
+        *reinterpret_cast<short8v*>(swz<D>(v_lds[buf], s_row0 + 1, s_col)) = sv1;
 #pragma unroll
         for (int j = 0; j < 8; j++) {
             unsigned p32 = ((unsigned)(unsigned short)sk0[j]) |
                            (((unsigned)(unsigned short)sk1[j]) << 16);
-            *reinterpret_cast<unsigned*>(swzb2<BLKN>(kt_lds[buf], s_col + j, s_row0)) = p32;
+            *reinterpret_cast<unsigned*>(swz<BLKN>(kt_lds[buf], s_col + j, s_row0)) = p32;
         }
     };
 
@@ -255,11 +182,11 @@ __global__ __launch_bounds__(FB2_BLOCK) void flash_bwd2_dq_kernel(
 #pragma unroll
             for (int kk = 0; kk < DSTEPS; kk++) {
                 frag8 ak = *reinterpret_cast<const frag8*>(
-                    swzb2<D>(k_lds[cur], sub * 32 + l32, kk * 16 + hi * 8));
+                    swz<D>(k_lds[cur], sub * 32 + l32, kk * 16 + hi * 8));
                 frag8 av = *reinterpret_cast<const frag8*>(
-                    swzb2<D>(v_lds[cur], sub * 32 + l32, kk * 16 + hi * 8));
-                st = mfma32b(ak, aq[kk], st);
-                dp = mfma32b(av, ado[kk], dp);
+                    swz<D>(v_lds[cur], sub * 32 + l32, kk * 16 + hi * 8));
+                st = mfma32(ak, aq[kk], st);
+                dp = mfma32(av, ado[kk], dp);
             }
             __builtin_amdgcn_s_setprio(0);
 
@@ -267,7 +194,7 @@ __global__ __launch_bounds__(FB2_BLOCK) void flash_bwd2_dq_kernel(
             // scale (all per-lane: q = l32)
 #pragma unroll
             for (int r = 0; r < 16; r++) {
-                int row = sub * 32 + crow32b(r, hi);
+                int row = sub * 32 + crow32(r, hi);
                 int kvg = kv_base + row;
                 bool vis = (kvg < Skv) && (qg < Sq) &&
                            (!causal || kvg <= qg + causal_off);
@@ -286,8 +213,8 @@ __global__ __launch_bounds__(FB2_BLOCK) void flash_bwd2_dq_kernel(
 #pragma unroll
                 for (int n = 0; n < NDT; n++) {
                     frag8 bkf = *reinterpret_cast<const frag8*>(
-                        swzb2<BLKN>(kt_lds[cur], n * 32 + l32, ks * 16 + hi * 8));
-                    acc_dq[n] = mfma32b(ads, bkf, acc_dq[n]);
+                        swz<BLKN>(kt_lds[cur], n * 32 + l32, ks * 16 + hi * 8));
+                    acc_dq[n] = mfma32(ads, bkf, acc_dq[n]);
                 }
             }
             __builtin_amdgcn_s_setprio(0);
@@ -315,7 +242,7 @@ __global__ __launch_bounds__(FB2_BLOCK) void flash_bwd2_dq_kernel(
     // epilogue: acc_dq C-layout [q][d] (col = d, row = q)
 #pragma unroll
     for (int r = 0; r < 16; r++) {
-        int qrow = qw + crow32b(r, hi);
+        int qrow = qw + crow32(r, hi);
         if (qrow >= Sq) continue;
         ushort_t* dqr = dq + ((long long)b * Sq + qrow) * q_row_stride + (long long)hq * D;
 #pragma unroll
@@ -448,18 +375,18 @@ __global__ __launch_bounds__(FB2_BLOCK, 1) void flash_bwd2_dkv_kernel(
             }
         };
         auto write_qtile = [&](int q_tb, int buf) {
-            *reinterpret_cast<short8v*>(swzb2<D>(q_lds[buf], s_row0, s_col)) = sq0;
-            *reinterpret_cast<short8v*>(swzb2<D>(q_lds[buf], s_row0 + 1, s_col)) = sq1;
-            *reinterpret_cast<short8v*>(swzb2<D>(do_lds[buf], s_row0, s_col)) = sd0;
-            *reinterpret_cast<short8v*>(swzb2<D>(do_lds[buf], s_row0 + 1, s_col)) = sd1;
+            *reinterpret_cast<short8v*>(swz<D>(q_lds[buf], s_row0, s_col)) = sq0;
+            *reinterpret_cast<short8v*>(swz<D>(q_lds[buf], s_row0 + 1, s_col)) = sq1;
+            *reinterpret_cast<short8v*>(swz<D>(do_lds[buf], s_row0, s_col)) = sd0;
+            *reinterpret_cast<short8v*>(swz<D>(do_lds[buf], s_row0 + 1, s_col)) = sd1;
 #pragma unroll
             for (int j = 0; j < 8; j++) {
                 unsigned pq = ((unsigned)(unsigned short)sq0[j]) |
                               (((unsigned)(unsigned short)sq1[j]) << 16);
                 unsigned pd = ((unsigned)(unsigned short)sd0[j]) |
                               (((unsigned)(unsigned short)sd1[j]) << 16);
-                *reinterpret_cast<unsigned*>(swzb2<BLKQ>(qt_lds[buf], s_col + j, s_row0)) = pq;
-                *reinterpret_cast<unsigned*>(swzb2<BLKQ>(dot_lds[buf], s_col + j, s_row0)) = pd;
+                *reinterpret_cast<unsigned*>(swz<BLKQ>(qt_lds[buf], s_col + j, s_row0)) = pq;
+                *reinterpret_cast<unsigned*>(swz<BLKQ>(dot_lds[buf], s_col + j, s_row0)) = pd;
             }
             if (tid < BLKQ) {
                 int qgl = q_tb + tid;
@@ -502,11 +429,11 @@ __global__ __launch_bounds__(FB2_BLOCK, 1) void flash_bwd2_dkv_kernel(
 #pragma unroll
                     for (int kk = 0; kk < DSTEPS; kk++) {
                         frag8 aqf = *reinterpret_cast<const frag8*>(
-                            swzb2<D>(q_lds[cur], sub * 32 + l32, kk * 16 + hi * 8));
+                            swz<D>(q_lds[cur], sub * 32 + l32, kk * 16 + hi * 8));
                         frag8 adf = *reinterpret_cast<const frag8*>(
-                            swzb2<D>(do_lds[cur], sub * 32 + l32, kk * 16 + hi * 8));
-                        st = mfma32b(aqf, bk[kk], st);
-                        dp = mfma32b(adf, bv[kk], dp);
+                            swz<D>(do_lds[cur], sub * 32 + l32, kk * 16 + hi * 8));
+                        st = mfma32(aqf, bk[kk], st);
+                        dp = mfma32(adf, bv[kk], dp);
                     }
                     __builtin_amdgcn_s_setprio(0);
 
@@ -515,7 +442,7 @@ __global__ __launch_bounds__(FB2_BLOCK, 1) void flash_bwd2_dkv_kernel(
                     // uniform per reg): lse/delta broadcast from LDS.
 #pragma unroll
                     for (int r = 0; r < 16; r++) {
-                        int qrow = sub * 32 + crow32b(r, hi);
+                        int qrow = sub * 32 + crow32(r, hi);
                         int qgl = q_tb + qrow;
                         float ls = lse_lds[cur][qrow];
                         float dl = dl_lds[cur][qrow];
@@ -539,11 +466,11 @@ __global__ __launch_bounds__(FB2_BLOCK, 1) void flash_bwd2_dkv_kernel(
 #pragma unroll
                         for (int n = 0; n < NDT; n++) {
                             frag8 bdo = *reinterpret_cast<const frag8*>(
-                                swzb2<BLKQ>(dot_lds[cur], n * 32 + l32, ks * 16 + hi * 8));
+                                swz<BLKQ>(dot_lds[cur], n * 32 + l32, ks * 16 + hi * 8));
                             frag8 bq = *reinterpret_cast<const frag8*>(
-                                swzb2<BLKQ>(qt_lds[cur], n * 32 + l32, ks * 16 + hi * 8));
-                            acc_dv[n] = mfma32b(apt, bdo, acc_dv[n]);
-                            acc_dk[n] = mfma32b(ads, bq, acc_dk[n]);
+                                swz<BLKQ>(qt_lds[cur], n * 32 + l32, ks * 16 + hi * 8));
+                            acc_dv[n] = mfma32(apt, bdo, acc_dv[n]);
+                            acc_dk[n] = mfma32(ads, bq, acc_dk[n]);
                         }
                     }
                     __builtin_amdgcn_s_setprio(0);
@@ -568,7 +495,7 @@ __global__ __launch_bounds__(FB2_BLOCK, 1) void flash_bwd2_dkv_kernel(
     const long long out_row_stride = (long long)Hk * D;
 #pragma unroll
     for (int r = 0; r < 16; r++) {
-        int kvr = kvw + crow32b(r, hi);
+        int kvr = kvw + crow32(r, hi);
         if (kvr >= Skv) continue;
         long long base = ((long long)b * Skv + kvr) * out_row_stride + (long long)hk * D;
 #pragma unroll
@@ -588,11 +515,7 @@ bool launch_flash_bwd2(const void* dout, const void* q, const void* k, const voi
                        int B, int Sq, int Skv, int Hq, int Hk, int D,
                        float scale, bool causal, hipStream_t stream) {
     if (D != 128 || (Hq % Hk) != 0) return false;
-    long long rows = (long long)B * Sq * Hq;
-    int waves_per_block = FB2_BLOCK / 64;
-    int dgrid = (int)((rows + waves_per_block - 1) / waves_per_block);
-    hipLaunchKernelGGL(flash_bwd2_delta_kernel<128>, dim3(dgrid), dim3(FB2_BLOCK), 0, stream,
-                       (const ushort_t*)dout, (const ushort_t*)o, delta, B, Sq, Hq);
+    launch_flash_bwd_delta(dout, o, delta, B, Sq, Hq, D, stream);
     dim3 gq((Sq + 255) / 256, B * Hq);
     hipLaunchKernelGGL((flash_bwd2_dq_kernel<128, false>), gq, dim3(FB2_BLOCK), 0, stream,
                        (const ushort_t*)q, (const ushort_t*)k, (const ushort_t*)v,
@@ -615,11 +538,7 @@ bool launch_flash_bwd2_mask(const void* dout, const void* q, const void* k,
                             int B, int Sq, int Skv, int Hq, int Hk, int D,
                             float scale, hipStream_t stream) {
     if (D != 128 || (Hq % Hk) != 0) return false;
-    long long rows = (long long)B * Sq * Hq;
-    int waves_per_block = FB2_BLOCK / 64;
-    int dgrid = (int)((rows + waves_per_block - 1) / waves_per_block);
-    hipLaunchKernelGGL(flash_bwd2_delta_kernel<128>, dim3(dgrid), dim3(FB2_BLOCK), 0, stream,
-                       (const ushort_t*)dout, (const ushort_t*)o, delta, B, Sq, Hq);
+    launch_flash_bwd_delta(dout, o, delta, B, Sq, Hq, D, stream);
     dim3 gq((Sq + 255) / 256, B * Hq);
     hipLaunchKernelGGL((flash_bwd2_dq_kernel<128, true>), gq, dim3(FB2_BLOCK), 0, stream,
                        (const ushort_t*)q, (const ushort_t*)k, (const ushort_t*)v,

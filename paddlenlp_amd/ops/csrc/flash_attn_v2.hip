@@ -25,7 +25,8 @@
 //
 // Reference behavior: paddle `flash_attention` fused op;
 // numerics oracle: tests/test_ops_gpu.py vs fp32 torch attention.
-#include "common.h"
+#include "launchers.h"
+#include "mfma.h"
 
 #define FA2_WAVES 8
 #define FA2_BLOCK (FA2_WAVES * 64)
@@ -33,31 +34,6 @@
 #define FA2_QW 32            // q rows per wave
 #define FA2_BLKM (FA2_WAVES * FA2_QW)
 #define DEFER_THR 8.0f
-
-typedef short8v frag8;
-
-__device__ __forceinline__ f32x16 mfma32(frag8 a, frag8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-
-// C/D layout of mfma_f32_32x32x16_bf16 (guide §3, HW-verified m74/m101):
-//   C[row][col]: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
-__device__ __forceinline__ int crow32(int r, int hi) {
-    return (r & 3) + 8 * (r >> 2) + 4 * hi;
-}
-
-// XOR swizzle for a row-major bf16 LDS tile (stride LD elements):
-// byte offset ^ ((row&7)<<4) — bijective within an 8-row stripe, keeps
-// 16B alignment so b128 reads/writes stay legal.
-template <int LD>
-__device__ __forceinline__ char* swz2(ushort_t* base, int row, int col_elem) {
-    return reinterpret_cast<char*>(base) +
-           (((row * LD + col_elem) * 2) ^ ((row & 7) << 4));
-}
-
-__device__ __forceinline__ unsigned pack_bf16(float a, float b) {
-    return (unsigned)f32_to_bf16(a) | ((unsigned)f32_to_bf16(b) << 16);
-}
 
 // ---------------------------------------------------------------------------
 // layout probe for mfma_f32_32x32x16_bf16: one wave computes C = A(32x16) @
@@ -207,13 +183,13 @@ __global__ __launch_bounds__(FA2_BLOCK) void flash_fwd2_kernel(
             se_lds[buf][tid] =
                 (g < Skv) ? startend[(long long)b * Skv + g] : 0;
         }
-        *reinterpret_cast<short8v*>(swz2<D>(k_lds[buf], s_row0, s_col)) = sk0;
-        *reinterpret_cast<short8v*>(swz2<D>(k_lds[buf], s_row0 + 1, s_col)) = sk1;
+        *reinterpret_cast<short8v*>(swz<D>(k_lds[buf], s_row0, s_col)) = sk0;
+        *reinterpret_cast<short8v*>(swz<D>(k_lds[buf], s_row0 + 1, s_col)) = sk1;
 #pragma unroll
         for (int j = 0; j < 8; j++) {
             unsigned p32 = ((unsigned)(unsigned short)sv0[j]) |
                            (((unsigned)(unsigned short)sv1[j]) << 16);
-            *reinterpret_cast<unsigned*>(swz2<FA2_BLKN>(vt_lds[buf], s_col + j, s_row0)) = p32;
+            *reinterpret_cast<unsigned*>(swz<FA2_BLKN>(vt_lds[buf], s_col + j, s_row0)) = p32;
         }
     };
 
@@ -261,7 +237,7 @@ __global__ __launch_bounds__(FA2_BLOCK) void flash_fwd2_kernel(
 #pragma unroll
                 for (int nt = 0; nt < KVT; nt++) {
                     frag8 ak = *reinterpret_cast<const frag8*>(
-                        swz2<D>(k_lds[cur], nt * 32 + l32, kk * 16 + hi * 8));
+                        swz<D>(k_lds[cur], nt * 32 + l32, kk * 16 + hi * 8));
                     st[nt] = mfma32(ak, aq[kk], st[nt]);
                 }
             }
@@ -363,37 +339,17 @@ __global__ __launch_bounds__(FA2_BLOCK) void flash_fwd2_kernel(
             l_run += ps;
 
             // P (C-layout, rows = kv) -> PV A-fragments, fully in-register
-            // (T12).  For k-step ks the lane needs P[q = l32][kv = ks*16 +
-            // hi*8 + j]; swap(pack(p0,p1), pack(p4,p5)) delivers words {0,2}
-            // and swap(pack(p2,p3), pack(p6,p7)) words {1,3}.
+            // (T12, mfma.h).  For k-step ks the lane needs P[q = l32][kv =
+            // ks*16 + hi*8 + j]: the 8-register slice (ks&1)*8 of sub-tile
+            // ks>>1.
             __builtin_amdgcn_s_setprio(1);
 #pragma unroll
             for (int ks = 0; ks < FA2_BLKN / 16; ks++) {
-                const int nt = ks >> 1;
-                const int rb = (ks & 1) * 8;   // reg base within the sub-tile
-                unsigned w[4];
-                {
-                    unsigned lo0 = pack_bf16(st[nt][rb + 0], st[nt][rb + 1]);
-                    unsigned hi0 = pack_bf16(st[nt][rb + 4], st[nt][rb + 5]);
-                    auto rr = __builtin_amdgcn_permlane32_swap(lo0, hi0, false, false);
-                    w[0] = rr[0]; w[2] = rr[1];
-                }
-                {
-                    unsigned lo1 = pack_bf16(st[nt][rb + 2], st[nt][rb + 3]);
-                    unsigned hi1 = pack_bf16(st[nt][rb + 6], st[nt][rb + 7]);
-                    auto rr = __builtin_amdgcn_permlane32_swap(lo1, hi1, false, false);
-                    w[1] = rr[0]; w[3] = rr[1];
-                }
-                frag8 pa;
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    pa[j * 2] = (short)(w[j] & 0xffff);
-                    pa[j * 2 + 1] = (short)(w[j] >> 16);
-                }
+                frag8 pa = t12_convert(st[ks >> 1], (ks & 1) * 8);
 #pragma unroll
                 for (int n = 0; n < NDT; n++) {
                     frag8 bv = *reinterpret_cast<const frag8*>(
-                        swz2<FA2_BLKN>(vt_lds[cur], n * 32 + l32, ks * 16 + hi * 8));
+                        swz<FA2_BLKN>(vt_lds[cur], n * 32 + l32, ks * 16 + hi * 8));
                     acc_o[n] = mfma32(pa, bv, acc_o[n]);
                 }
             }

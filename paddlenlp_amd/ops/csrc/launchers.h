@@ -1,0 +1,152 @@
+// Host-side launcher prototypes for the gfx950 kernel pack.  Included by
+// bindings.cpp and by every .hip file that defines or calls a launcher, so a
+// signature that drifts fails to compile in the defining file.
+#pragma once
+
+#include <hip/hip_runtime_api.h>
+
+#include <stdexcept>
+#include <string>
+
+// A head dim without a compiled kernel is an error, never a silent no-op.
+[[noreturn]] inline void unsupported_head_dim(const char* op, int D) {
+    throw std::runtime_error(std::string(op) + ": no kernel for head dim " +
+                             std::to_string(D));
+}
+
+// ---- rms_norm.hip / rope.hip / swiglu.hip / cross_entropy.hip ----
+void launch_rms_norm_fwd(const void* x, const void* w, void* y, float* invrms,
+                         long long rows, int H, float eps, hipStream_t stream);
+void launch_rms_norm_bwd(const void* dy, const void* x, const void* w,
+                         const float* invrms, void* dx, float* dw_partial,
+                         float* dw32, void* dw, bool dw_is_bf16,
+                         long long rows, int H, int P, hipStream_t stream);
+void launch_rope(const void* x, void* out, const float* cos_t, const float* sin_t,
+                 long long n_rows, int H, int D, int S, bool backward,
+                 hipStream_t stream);
+void launch_swiglu_fwd(const void* x, void* y, long long N, int I, hipStream_t stream);
+void launch_swiglu_bwd(const void* dy, const void* x, void* dx, long long N, int I,
+                       hipStream_t stream);
+void launch_ce_fwd(const void* logits, const long long* labels, float* loss,
+                   float* maxlse, long long N, int V, long long ignore_index,
+                   hipStream_t stream);
+void launch_ce_bwd(const float* dloss, const void* logits, const long long* labels,
+                   const float* maxlse, void* dlogits, long long N, int V,
+                   long long ignore_index, hipStream_t stream);
+
+// ---- adamw.hip ----
+struct AdamWChunk {
+    void* param;       // bf16 or fp32
+    const void* grad;  // matches param dtype
+    float* m;
+    float* v;
+    float* master;     // nullptr when param is fp32
+    long long offset;  // element offset of this chunk within the tensor
+    long long n;       // elements in this chunk
+    int is_bf16;
+};
+void launch_adamw(const AdamWChunk* dev_chunks, int n_chunks,
+                  float lr, float beta1, float beta2, float eps, float wd,
+                  float bias1, float bias2, hipStream_t stream);
+
+// ---- flash_attn.hip: public attention entry points.  The default tries the
+// v2 (D=128) kernels and falls back to v1; force_v1 skips v2. ----
+void launch_mfma_probe(const void* A, const void* B, float* C, hipStream_t stream);
+void launch_flash_fwd(const void* q, const void* k, const void* v, void* o,
+                      float* lse, int B, int Sq, int Skv, int Hq, int Hk, int D,
+                      float scale, bool causal, bool force_v1, hipStream_t stream);
+void launch_flash_bwd(const void* dout, const void* q, const void* k, const void* v,
+                      const void* o, const float* lse, float* delta,
+                      void* dq, void* dk, void* dv,
+                      int B, int Sq, int Skv, int Hq, int Hk, int D,
+                      float scale, bool causal, bool force_v1, hipStream_t stream);
+void launch_flash_fwd_mask(const void* q, const void* k, const void* v, void* o,
+                           float* lse, const int* startend,
+                           int B, int Sq, int Skv, int Hq, int Hk, int D,
+                           float scale, hipStream_t stream);
+void launch_flash_bwd_mask(const void* dout, const void* q, const void* k, const void* v,
+                           const void* o, const float* lse, float* delta,
+                           void* dq, void* dk, void* dv, const int* startend,
+                           int B, int Sq, int Skv, int Hq, int Hk, int D,
+                           float scale, hipStream_t stream);
+// delta[b,h,q] = rowsum(dO * O), shared by the v1 and v2 backward
+void launch_flash_bwd_delta(const void* dout, const void* o, float* delta,
+                            int B, int Sq, int Hq, int D, hipStream_t stream);
+
+// ---- flash_attn_v2.hip / flash_attn_bwd_v2.hip: 8-wave 32x32 kernels.
+// Return false (nothing launched) when the shape is not theirs. ----
+void launch_mfma32_probe(const void* A, const void* B, float* C, hipStream_t stream);
+void launch_permlane_probe(int* out0, int* out1, hipStream_t stream);
+bool launch_flash_fwd2(const void* q, const void* k, const void* v, void* o,
+                       float* lse, int B, int Sq, int Skv, int Hq, int Hk,
+                       int D, float scale, bool causal, hipStream_t stream);
+bool launch_flash_fwd2_mask(const void* q, const void* k, const void* v,
+                            void* o, float* lse, const int* startend,
+                            int B, int Sq, int Skv, int Hq, int Hk,
+                            int D, float scale, hipStream_t stream);
+bool launch_flash_bwd2(const void* dout, const void* q, const void* k, const void* v,
+                       const void* o, const float* lse, float* delta,
+                       void* dq, void* dk, void* dv,
+                       int B, int Sq, int Skv, int Hq, int Hk, int D,
+                       float scale, bool causal, hipStream_t stream);
+bool launch_flash_bwd2_mask(const void* dout, const void* q, const void* k,
+                            const void* v, const void* o, const float* lse,
+                            float* delta, void* dq, void* dk, void* dv,
+                            const int* startend,
+                            int B, int Sq, int Skv, int Hq, int Hk, int D,
+                            float scale, hipStream_t stream);
+
+// ---- paged_attn.hip / paged_attn_v2.hip ----
+int paged_decode_nsplit(int B, int Hk);
+void launch_paged_decode_attn(const void* q, const void* k_cache, const void* v_cache,
+                              const float* k_scale, const float* v_scale,
+                              const int* block_table, const int* seq_lens, void* out,
+                              float* partials, int nsplit,
+                              int B, int Hq, int Hk, int D, int block_size,
+                              int max_blocks, float scale, int cache_mode,
+                              hipStream_t stream);
+// MFMA decode kernel; false (nothing launched) unless D==128 and G<=16.
+// Writes out (nsplit == 1) or the partials the split-merge kernel consumes.
+bool launch_paged_decode_attn3(const void* q, const void* k_cache, const void* v_cache,
+                               const float* k_scale, const float* v_scale,
+                               const int* block_table, const int* seq_lens, void* out,
+                               float* partials, int nsplit,
+                               int B, int Hq, int Hk, int D, int block_size,
+                               int max_blocks, float scale, int cache_mode,
+                               hipStream_t stream);
+void launch_rope_cache_append(const void* qkv, void* q_out, void* k_cache, void* v_cache,
+                              float* k_scale, float* v_scale,
+                              const int* block_table, const int* seq_lens_before,
+                              const float* cos_t, const float* sin_t,
+                              int B, int T, int Hq, int Hk, int D, int block_size,
+                              int max_blocks, const int* token_counts,
+                              int cache_mode, hipStream_t stream);
+
+// ---- wint8_gemv.hip / skinny_gemm.hip ----
+void launch_wint8_gemv(const void* x, const void* wq, const float* scale, void* y,
+                       int M, int N, int K, hipStream_t stream);
+void launch_fp8_rowwise_quant(const void* x, void* y, float* scales,
+                              long long R, int K, hipStream_t stream);
+int skinny_gemm_ksplit(int N, int K, int ksplit_req);
+void launch_skinny_gemm(const void* x, const void* w, float* partial, void* y,
+                        int M, int N, int K, int ksplit, hipStream_t stream);
+
+// ---- sampling.hip ----
+void launch_repetition_penalty(void* logits, const long long* pre_ids,
+                               const int* pre_lens, const float* rep_pen,
+                               int B, long long V, int max_len, hipStream_t s);
+void launch_topp_sample(const void* logits, const float* temperature,
+                        const float* top_p, const float* uniform,
+                        const long long* ban_eos, int n_ban,
+                        const int* cur_lens, const int* min_lens,
+                        long long* out, int B, long long V, hipStream_t s);
+void launch_decode_update(long long* tokens, signed char* stop_flags,
+                          const signed char* active, long long* pre_ids,
+                          int* pre_lens, int* seq_lens,
+                          const long long* eos_ids, int n_eos,
+                          int* not_need_stop, const int* max_new,
+                          long long pad_id, int B, int max_len, hipStream_t s);
+void launch_block_step(int* block_table, int* seq_lens, signed char* stop_flags,
+                       signed char* active, int* free_list, int* free_count,
+                       signed char* is_block_step, int B, int block_size,
+                       int max_blocks, hipStream_t s);

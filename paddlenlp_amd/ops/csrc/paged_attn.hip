@@ -10,7 +10,7 @@
 //
 // Cache layout: [num_blocks, block_size, Hk, D] bf16 per layer.
 #include "common.h"
-#include <cstdlib>
+#include "launchers.h"
 
 #define PA_WAVES 4
 #define PA_BLOCK (PA_WAVES * 64)
@@ -455,22 +455,6 @@ int paged_decode_nsplit(int B, int Hk) {
     return nsplit;
 }
 
-// v2/v3 (paged_attn_v2.hip): MFMA-tiled cooperative-staging decode kernels
-bool launch_paged_decode_attn3(const void* q, const void* k_cache, const void* v_cache,
-                               const float* k_scale, const float* v_scale,
-                               const int* block_table, const int* seq_lens, void* out,
-                               float* partials, int nsplit,
-                               int B, int Hq, int Hk, int D, int block_size,
-                               int max_blocks, float scale, int cache_mode,
-                               hipStream_t stream);
-bool launch_paged_decode_attn2(const void* q, const void* k_cache, const void* v_cache,
-                               const float* k_scale, const float* v_scale,
-                               const int* block_table, const int* seq_lens, void* out,
-                               float* partials, int nsplit,
-                               int B, int Hq, int Hk, int D, int block_size,
-                               int max_blocks, float scale, int cache_mode,
-                               hipStream_t stream);
-
 void launch_paged_decode_attn(const void* q, const void* k_cache, const void* v_cache,
                               const float* k_scale, const float* v_scale,
                               const int* block_table, const int* seq_lens, void* out,
@@ -478,44 +462,36 @@ void launch_paged_decode_attn(const void* q, const void* k_cache, const void* v_
                               int B, int Hq, int Hk, int D, int block_size,
                               int max_blocks, float scale, int cache_mode,
                               hipStream_t stream) {
-    static const char* kver = getenv("PNLP_DECODE_KERNEL");  // "2" forces v2
-    const bool want_v2 = (kver != nullptr && kver[0] == '2');
-    if ((!want_v2 &&
-         launch_paged_decode_attn3(q, k_cache, v_cache, k_scale, v_scale,
+    if (D != 128 && D != 64) unsupported_head_dim("paged decode attention", D);
+    // main kernel: the MFMA kernel (paged_attn_v2.hip) when it accepts the
+    // shape, otherwise the scalar v1 kernel
+    if (!launch_paged_decode_attn3(q, k_cache, v_cache, k_scale, v_scale,
                                    block_table, seq_lens, out, partials, nsplit,
                                    B, Hq, Hk, D, block_size, max_blocks, scale,
-                                   cache_mode, stream)) ||
-        launch_paged_decode_attn2(q, k_cache, v_cache, k_scale, v_scale,
-                                  block_table, seq_lens, out, partials, nsplit,
-                                  B, Hq, Hk, D, block_size, max_blocks, scale,
-                                  cache_mode, stream)) {
-        if (nsplit > 1) {
-            if (D == 128)
-                hipLaunchKernelGGL(paged_decode_merge_kernel<128>, dim3(B, Hk, Hq / Hk),
-                                   dim3(64), 0, stream, partials, (ushort_t*)out,
-                                   seq_lens, B, Hq, Hk, nsplit);
-        }
-        return;
-    }
-    dim3 grid(B, Hk, nsplit);
-    const bool c8 = (k_scale != nullptr);
+                                   cache_mode, stream)) {
+        dim3 grid(B, Hk, nsplit);
+        const bool c8 = (k_scale != nullptr);
 #define PA_LAUNCH(DD, CC)                                                          \
     hipLaunchKernelGGL((paged_decode_attn_kernel<DD, CC>), grid, dim3(PA_BLOCK),   \
                        0, stream, (const ushort_t*)q, k_cache, v_cache,            \
                        k_scale, v_scale, block_table, seq_lens, (ushort_t*)out,    \
                        partials, B, Hq, Hk, block_size, max_blocks, scale, nsplit)
-    if (D == 128) {
-        if (c8) PA_LAUNCH(128, true); else PA_LAUNCH(128, false);
-        if (nsplit > 1)
-            hipLaunchKernelGGL(paged_decode_merge_kernel<128>, dim3(B, Hk, Hq / Hk), dim3(64),
-                               0, stream, partials, (ushort_t*)out, seq_lens, B, Hq, Hk, nsplit);
-    } else if (D == 64) {
-        if (c8) PA_LAUNCH(64, true); else PA_LAUNCH(64, false);
-        if (nsplit > 1)
-            hipLaunchKernelGGL(paged_decode_merge_kernel<64>, dim3(B, Hk, Hq / Hk), dim3(64),
-                               0, stream, partials, (ushort_t*)out, seq_lens, B, Hq, Hk, nsplit);
-    }
+        if (D == 128) {
+            if (c8) PA_LAUNCH(128, true); else PA_LAUNCH(128, false);
+        } else {
+            if (c8) PA_LAUNCH(64, true); else PA_LAUNCH(64, false);
+        }
 #undef PA_LAUNCH
+    }
+    if (nsplit > 1) {
+        dim3 mgrid(B, Hk, Hq / Hk);
+        if (D == 128)
+            hipLaunchKernelGGL(paged_decode_merge_kernel<128>, mgrid, dim3(64), 0, stream,
+                               partials, (ushort_t*)out, seq_lens, B, Hq, Hk, nsplit);
+        else
+            hipLaunchKernelGGL(paged_decode_merge_kernel<64>, mgrid, dim3(64), 0, stream,
+                               partials, (ushort_t*)out, seq_lens, B, Hq, Hk, nsplit);
+    }
 }
 
 void launch_rope_cache_append(const void* qkv, void* q_out, void* k_cache, void* v_cache,
@@ -538,6 +514,8 @@ void launch_rope_cache_append(const void* qkv, void* q_out, void* k_cache, void*
         else RC_LAUNCH(128, 0);
     } else if (D == 64) {
         if (cache_mode == 1) RC_LAUNCH(64, 1); else RC_LAUNCH(64, 0);
+    } else {
+        unsupported_head_dim("rope_cache_append", D);
     }
 #undef RC_LAUNCH
 }

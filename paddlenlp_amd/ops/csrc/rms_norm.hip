@@ -8,6 +8,7 @@
 // bwd:  dx = invrms * (dy*w - x * invrms^2 * mean(dy*w*x))
 //       dw = sum_rows(dy * x * invrms)   (two-pass partial reduction)
 #include "common.h"
+#include "launchers.h"
 
 #define RMS_BLOCK 256
 

@@ -8,6 +8,7 @@
 //   out[..., i+D/2]   = x[i+D/2] * cos[i+D/2] + x[i] * sin[i+D/2]
 // backward = rotation by -theta (sign flip on sin).
 #include "common.h"
+#include "launchers.h"
 
 // one thread handles 4 (i, i+D/2) pairs => 8 bf16 loads/stores, coalesced
 // within the half-rows.  Layout: token-row = (b*S + s)*H*D + h*D.

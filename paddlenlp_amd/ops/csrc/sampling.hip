@@ -22,6 +22,7 @@
 //     free list is empty the longest running sequence is preempted
 //     (flagged in is_block_step for host-side recovery/refill).
 #include "common.h"
+#include "launchers.h"
 #include <hip/hip_runtime.h>
 
 // ---------------------------------------------------------------------------

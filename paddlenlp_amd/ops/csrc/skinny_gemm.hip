@@ -21,6 +21,7 @@
 // deterministic split-K GEMM (useful reference / TP-shard shapes) but the
 // engine keeps hipBLASLt for decode projections.
 #include "common.h"
+#include "launchers.h"
 
 #define SG_WAVES 4
 #define SG_BLOCK (SG_WAVES * 64)

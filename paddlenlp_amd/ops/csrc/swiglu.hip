@@ -6,6 +6,7 @@
 // bwd:  dg = dy * u * silu'(g);  du = dy * silu(g)
 //       silu(g) = g * sigmoid(g); silu'(g) = sig(g) * (1 + g * (1 - sig(g)))
 #include "common.h"
+#include "launchers.h"
 
 __global__ void swiglu_fwd_kernel(
     const ushort_t* __restrict__ x, ushort_t* __restrict__ y,

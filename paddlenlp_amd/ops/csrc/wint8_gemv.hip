@@ -9,6 +9,7 @@
 // dequantize in-register and dot against an x chunk staged in LDS as fp32
 // (same-address broadcast reads are conflict-free).
 #include "common.h"
+#include "launchers.h"
 #include <hip/hip_fp8.h>
 
 #define WG_BLOCK 256

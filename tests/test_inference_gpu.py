@@ -35,6 +35,28 @@ def test_paged_decode_attn(C):
         (out.cpu().float() - ref.float()).abs().max()
 
 
+def test_paged_decode_attn_d64_split_merge(C):
+    """D=64 runs the v1 scalar kernel; B*Hk=4 forces nsplit > 1, so the
+    partials go through paged_decode_merge_kernel<64>."""
+    from paddlenlp_amd.experimental.fused_transformer import paged_decode_attn_ref
+
+    torch.manual_seed(0)
+    B, Hq, Hk, D = 2, 4, 2, 64
+    bs, nblocks, max_blocks = 16, 16, 5
+    q = torch.randn(B, Hq, D, device="cuda", dtype=torch.bfloat16)
+    k_cache = torch.randn(nblocks, bs, Hk, D, device="cuda", dtype=torch.bfloat16)
+    v_cache = torch.randn(nblocks, bs, Hk, D, device="cuda", dtype=torch.bfloat16)
+    perm = torch.randperm(nblocks)[: B * max_blocks].reshape(B, max_blocks)
+    block_table = perm.to(torch.int32).cuda()
+    seq_lens = torch.tensor([5, 70], dtype=torch.int32, device="cuda")
+
+    out = C.paged_decode_attn(q, k_cache, v_cache, block_table, seq_lens)
+    ref = paged_decode_attn_ref(q.cpu(), k_cache.cpu(), v_cache.cpu(),
+                                block_table.cpu(), seq_lens.cpu())
+    assert torch.allclose(out.cpu().float(), ref.float(), atol=3e-2, rtol=3e-2), \
+        (out.cpu().float() - ref.float()).abs().max()
+
+
 def test_rope_cache_append(C):
     from paddlenlp_amd.experimental.fused_transformer import rope_cache_append_ref
     from paddlenlp_amd import ops

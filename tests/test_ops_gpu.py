@@ -137,6 +137,7 @@ def test_swiglu_fwd_bwd(C):
     (1, 64, 192, 2, 2, 128, True),      # Skv > Sq (cached decode pattern)
     (1, 128, 64, 2, 2, 128, False),     # Sq > Skv non-causal (zigzag CP block)
     (1, 64, 128, 2, 2, 128, False),     # Skv > Sq non-causal (zigzag CP block)
+    (1, 64, 192, 2, 2, 64, False),      # v1 (D=64) non-causal, Sq != Skv
 ])
 def test_flash_attention_fwd(C, B, Sq, Skv, Hq, Hk, D, causal):
     from paddlenlp_amd import ops
@@ -419,3 +420,93 @@ def test_flashmask_bench_shape_gqa(C):
                                         causal=True, startend_row_indices=se)
     assert torch.allclose(out.float(), ref, atol=3e-2, rtol=3e-2), \
         (out.float() - ref).abs().max()
+
+
+def _rand_qkv(B, S, Hq, Hk, D):
+    q = _bf16(torch.randn(B, S, Hq, D, device="cuda"))
+    k = _bf16(torch.randn(B, S, Hk, D, device="cuda"))
+    v = _bf16(torch.randn(B, S, Hk, D, device="cuda"))
+    return q, k, v
+
+
+def _check_fwd_bwd_vs_reference(attn, q, k, v, **ref_kwargs):
+    """attn(q, k, v, dout) -> (out, dq, dk, dv), compared with the fp32
+    reference at the file's 3e-2 forward / 5e-2 backward tolerances."""
+    from paddlenlp_amd import ops
+
+    dout = _bf16(torch.randn(q.shape, device="cuda"))
+    out, dq, dk, dv = attn(q, k, v, dout)
+    qr, kr, vr = (t.float().requires_grad_() for t in (q, k, v))
+    ref = ops.reference.flash_attention(qr, kr, vr, causal=True, **ref_kwargs)
+    ref.backward(dout.float())
+    assert torch.allclose(out.float(), ref, atol=3e-2, rtol=3e-2), \
+        (out.float() - ref).abs().max()
+    for g, gr, name in ((dq, qr.grad, "dq"), (dk, kr.grad, "dk"), (dv, vr.grad, "dv")):
+        assert torch.allclose(g.float(), gr, atol=5e-2, rtol=5e-2), \
+            (name, (g.float() - gr).abs().max())
+
+
+def _autograd_attn(**kwargs):
+    from paddlenlp_amd import ops
+
+    def attn(q, k, v, dout):
+        q, k, v = (t.clone().requires_grad_() for t in (q, k, v))
+        out = ops.flash_attention(q, k, v, causal=True, **kwargs)
+        out.backward(dout)
+        return out.detach(), q.grad, k.grad, v.grad
+    return attn
+
+
+@pytest.mark.parametrize("B,S,Hq,Hk,D", [
+    (1, 100, 2, 2, 64),      # ragged second tile
+    (2, 192, 4, 2, 64),      # three tiles, GQA
+    (1, 130, 2, 1, 32),      # head dim 32, two rows into the third tile
+])
+def test_flash_attention_v1_small_head_dims(C, B, S, Hq, Hk, D):
+    """D=64/32 always run the v1 (16x16x32, 64-row tile) kernels."""
+    torch.manual_seed(0)
+    q, k, v = _rand_qkv(B, S, Hq, Hk, D)
+    _check_fwd_bwd_vs_reference(_autograd_attn(), q, k, v)
+
+
+def test_flashmask_attention_v1_d64(C):
+    """v1 FlashMask fwd+bwd: packed boundaries 50/130/192, none tile-aligned."""
+    torch.manual_seed(0)
+    B, S, Hq, Hk, D = 2, 192, 4, 2, 64
+    q, k, v = _rand_qkv(B, S, Hq, Hk, D)
+    se = torch.empty(B, 1, S, 1, dtype=torch.int32, device="cuda")
+    lo = 0
+    for hi in (50, 130, 192):
+        se[:, 0, lo:hi, 0] = hi
+        lo = hi
+    _check_fwd_bwd_vs_reference(_autograd_attn(startend_row_indices=se), q, k, v,
+                                startend_row_indices=se)
+
+
+@pytest.mark.parametrize("B,S,Hq,Hk,D", [
+    (1, 100, 2, 2, 128),
+    (1, 192, 4, 2, 128),
+])
+def test_flash_attention_v1_forced_d128(C, B, S, Hq, Hk, D):
+    """force_v1 runs the v1 fallback kernels at the head dim v2 normally owns."""
+    torch.manual_seed(0)
+    q, k, v = _rand_qkv(B, S, Hq, Hk, D)
+
+    def attn(q, k, v, dout):
+        o, lse = C.flash_attn_fwd_ex(q, k, v, True, True)
+        dq, dk, dv = C.flash_attn_bwd_ex(dout, q, k, v, o, lse, True, True)
+        return o, dq, dk, dv
+    _check_fwd_bwd_vs_reference(attn, q, k, v)
+
+
+def test_flash_attention_rejects_unsupported_head_dim(C):
+    """D=48 has no kernel: the host-side check raises before any launch."""
+    B, S, H, D = 1, 64, 2, 48
+    q, k, v = _rand_qkv(B, S, H, H, D)
+    o = torch.zeros_like(q)
+    lse = torch.zeros(B, H, S, device="cuda", dtype=torch.float32)
+    se = torch.full((B, S), S, dtype=torch.int32, device="cuda")
+    with pytest.raises(RuntimeError):
+        C.flash_attn_bwd(torch.ones_like(q), q, k, v, o, lse, True)
+    with pytest.raises(RuntimeError):
+        C.flashmask_attn_fwd(q, k, v, se)

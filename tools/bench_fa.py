@@ -1,6 +1,6 @@
 """Within-probe A/B microbenchmark for the flash-attention kernels.
 
-Guide rule #13: cross-run/cross-box deltas under 10% are noise — variants
+Guide rule #13: cross-run/cross-box deltas under 10% are noise — kernels
 must be timed interleaved in ONE process on ONE box.
 """
 import argparse
@@ -14,7 +14,29 @@ import torch
 
 from paddlenlp_amd.ops.functional import _load_extension
 
-VARIANTS = {6: "v2-32x32", 7: "v1-linear", 5: "MF1+pipe"}
+# name -> force_v1: the default path (v2 8-wave 32x32 kernels at D=128) against
+# the v1 4-wave 16x16 fallback
+KERNELS = {"v2-32x32": False, "v1-linear": True}
+
+
+def _time_interleaved(fn, reps):
+    """Per-kernel wall times with the kernels alternating inside each rep."""
+    results = {name: [] for name in KERNELS}
+    for _ in range(reps):
+        for name, force_v1 in KERNELS.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn(force_v1)
+            torch.cuda.synchronize()
+            results[name].append(time.perf_counter() - t0)
+    return results
+
+
+def _report(tag, results, flops):
+    for name, times in results.items():
+        ts = sorted(times)[1:-1] or times  # trim outliers
+        mean = sum(ts) / len(ts)
+        print(f"  {tag} {name:<9}: {mean*1e3:8.2f} ms  {flops/mean/1e12:7.1f} TF/s")
 
 
 def main():
@@ -37,51 +59,27 @@ def main():
     # causal attention matmul FLOPs (0.5 visibility): 2 matmuls x 2 flops
     flops = 0.5 * 2 * 2 * args.B * args.Hq * args.S * args.S * args.D
 
-    # correctness cross-check between variants first
-    ref_o, ref_lse = C.flash_attn_fwd_ex(q, k, v, True, 7)
-    for var in VARIANTS:
-        o, lse = C.flash_attn_fwd_ex(q, k, v, True, var)
-        err = (o.float() - ref_o.float()).abs().max().item()
-        print(f"  variant {var} vs v1 max err: {err:.4f}")
-        assert err < 3e-2, (var, err)
-
-    results = {v: [] for v in VARIANTS}
-    for rep in range(args.reps):
-        for var in VARIANTS:  # interleaved
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            C.flash_attn_fwd_ex(q, k, v, True, var)
-            torch.cuda.synchronize()
-            results[var].append(time.perf_counter() - t0)
+    # correctness cross-check first: v2 against v1
+    ref_o, ref_lse = C.flash_attn_fwd_ex(q, k, v, True, True)
+    o, lse = C.flash_attn_fwd_ex(q, k, v, True, False)
+    err = (o.float() - ref_o.float()).abs().max().item()
+    print(f"  fwd v2 vs v1 max err: {err:.4f}")
+    assert err < 3e-2, err
 
     print(f"shape B{args.B} S{args.S} Hq{args.Hq} Hk{args.Hk} D{args.D}, {args.reps} reps:")
-    for var, name in VARIANTS.items():
-        ts = sorted(results[var])[1:-1] or results[var]  # trim outliers
-        mean = sum(ts) / len(ts)
-        print(f"  fwd variant {var} ({name:<11}): {mean*1e3:8.2f} ms  {flops/mean/1e12:7.1f} TF/s")
+    _report("fwd", _time_interleaved(
+        lambda force_v1: C.flash_attn_fwd_ex(q, k, v, True, force_v1), args.reps), flops)
 
-    # backward variants A/B (2=v2, 3=v1 linear)
-    o, lse = C.flash_attn_fwd_ex(q, k, v, True, 0)
     do = torch.randn_like(o)
-    ref_dq, ref_dk, ref_dv = C.flash_attn_bwd_ex(do, q, k, v, o, lse, True, 3)
-    dq2, dk2, dv2 = C.flash_attn_bwd_ex(do, q, k, v, o, lse, True, 2)
+    ref_dq, ref_dk, ref_dv = C.flash_attn_bwd_ex(do, q, k, v, o, lse, True, True)
+    dq2, dk2, dv2 = C.flash_attn_bwd_ex(do, q, k, v, o, lse, True, False)
     for nm, a, b in (("dq", ref_dq, dq2), ("dk", ref_dk, dk2), ("dv", ref_dv, dv2)):
         err = (a.float() - b.float()).abs().max().item()
         print(f"  bwd v2 vs v1 {nm} max err: {err:.4f}")
-    bres = {2: [], 3: []}
-    for rep in range(args.reps):
-        for var in (2, 3):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            C.flash_attn_bwd_ex(do, q, k, v, o, lse, True, var)
-            torch.cuda.synchronize()
-            bres[var].append(time.perf_counter() - t0)
     bwd_flops = flops * 3.5  # 7 matmuls vs fwd's 2
-    for var, name in ((2, "v2-32x32"), (3, "v1-linear")):
-        ts = sorted(bres[var])[1:-1] or bres[var]
-        mean = sum(ts) / len(ts)
-        print(f"  bwd variant {var} ({name:<9}): {mean*1e3:8.2f} ms  {bwd_flops/mean/1e12:7.1f} TF/s")
-
+    _report("bwd", _time_interleaved(
+        lambda force_v1: C.flash_attn_bwd_ex(do, q, k, v, o, lse, True, force_v1),
+        args.reps), bwd_flops)
 
 if __name__ == "__main__":
     main()
