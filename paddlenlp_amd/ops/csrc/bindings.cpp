@@ -206,6 +206,19 @@ std::vector<torch::Tensor> permlane_probe() {
     return {o0, o1};
 }
 
+// dual-use LDS image probe: X [64,128] bf16 -> (row view, transposed view)
+std::vector<torch::Tensor> lds_image_probe(torch::Tensor X) {
+    CHECK_GPU(X); CHECK_BF16(X);
+    TORCH_CHECK(X.dim() == 2 && X.size(0) == 64 && X.size(1) == 128,
+                "lds_image_probe: X must be [64,128]");
+    auto Xc = X.contiguous();
+    auto out_row = torch::empty_like(Xc);
+    auto out_tr = torch::empty_like(Xc);
+    launch_lds_image_probe(Xc.data_ptr(), out_row.data_ptr(), out_tr.data_ptr(),
+                           cur_stream());
+    return {out_row, out_tr};
+}
+
 // ---------------------------------------------------------------------------
 // flash attention.  Every entry point validates through check_attn_args, so
 // a shape without a kernel is an error before anything is launched.
@@ -296,6 +309,34 @@ std::vector<torch::Tensor> flash_attn_bwd(torch::Tensor dout, torch::Tensor q,
                                           torch::Tensor o, torch::Tensor lse,
                                           bool causal) {
     return flash_attn_bwd_ex(dout, q, k, v, o, lse, causal, /*force_v1=*/false);
+}
+
+// The v2 backward with only some of its launches (FLASH_BWD_* mask: 1 delta,
+// 2 dq, 4 dkv), so tools/bench_fa.py can time dq and dkv on their own.
+// Outputs of launches left out are uninitialised.
+std::vector<torch::Tensor> flash_attn_bwd2_parts(torch::Tensor dout, torch::Tensor q,
+                                                 torch::Tensor k, torch::Tensor v,
+                                                 torch::Tensor o, torch::Tensor lse,
+                                                 torch::Tensor delta, bool causal,
+                                                 int64_t parts) {
+    check_attn_args(q, k, v, &dout, &o, &lse);
+    TORCH_CHECK(delta.is_cuda() && delta.is_contiguous() &&
+                    delta.scalar_type() == torch::kFloat32 &&
+                    delta.sizes() == lse.sizes(),
+                "delta must be a contiguous fp32 GPU tensor shaped like lse");
+    int B = q.size(0), Sq = q.size(1), Hq = q.size(2), D = q.size(3);
+    int Skv = k.size(1), Hk = k.size(2);
+    auto dq = torch::empty_like(q);
+    auto dk_h = torch::empty({B, Skv, Hk, D}, k.options());
+    auto dv_h = torch::empty({B, Skv, Hk, D}, v.options());
+    float scale = 1.0f / std::sqrt((float)D);
+    TORCH_CHECK(launch_flash_bwd2(dout.data_ptr(), q.data_ptr(), k.data_ptr(),
+                                  v.data_ptr(), o.data_ptr(), lse.data_ptr<float>(),
+                                  delta.data_ptr<float>(), dq.data_ptr(),
+                                  dk_h.data_ptr(), dv_h.data_ptr(), B, Sq, Skv, Hq,
+                                  Hk, D, scale, causal, cur_stream(), (int)parts),
+                "flash_attn_bwd2_parts: no v2 kernel for this shape");
+    return {dq, dk_h, dv_h};
 }
 
 // ---------------------------------------------------------------------------
@@ -506,6 +547,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("mfma_probe", &mfma_probe);
     m.def("mfma32_probe", &mfma32_probe);
     m.def("permlane_probe", &permlane_probe);
+    m.def("lds_image_probe", &lds_image_probe);
+    m.def("flash_attn_bwd2_parts", &flash_attn_bwd2_parts);
     m.def("apply_repetition_penalty", &apply_repetition_penalty);
     m.def("topp_sample", &topp_sample,
           py::arg("logits"), py::arg("temperature"), py::arg("top_p"),

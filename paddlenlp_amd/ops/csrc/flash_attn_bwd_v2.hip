@@ -56,18 +56,10 @@ __global__ __launch_bounds__(FB2_BLOCK) void flash_bwd2_dq_kernel(
     const int l32 = lane & 31;
     const int hi = lane >> 5;
 
-    // XCD-aware remap (see flash_attn_v2.hip): keep one (b,h)'s tiles
-    // on one XCD so the shared K/V (dq) tiles re-hit that XCD's L2
+    // one (b,h)'s tiles stay on one XCD (shared K/V re-hit its L2); heaviest
+    // q tiles first (see mfma.h xcd_grouped_tile)
     int qt, bh;
-    if ((gridDim.y & 7) == 0) {
-        const int flat = blockIdx.x + gridDim.x * blockIdx.y;
-        const int idx = flat >> 3;
-        qt = idx % gridDim.x;
-        bh = (flat & 7) * (gridDim.y >> 3) + idx / gridDim.x;
-    } else {
-        qt = blockIdx.x;
-        bh = blockIdx.y;
-    }
+    xcd_grouped_tile<FA_ORDER_W, false>(qt, bh);
     const int b = bh / Hq, hq = bh % Hq;
     const int hk = hq / (Hq / Hk);
     const int q_base = qt * BLKM;
@@ -255,6 +247,14 @@ __global__ __launch_bounds__(FB2_BLOCK) void flash_bwd2_dq_kernel(
 // dKV kernel: kv stationary (8 waves x 32 kv = 256 kv rows/block), q iterated
 // in tiles of 64 across the whole GQA group.  Orientation: S and dP in
 // C-layout [q][kv] (col = kv) so T12 feeds dV += P^T·dO and dK += dS^T·Q.
+//
+// Staging: each 64 x 128 Q and dO tile lives in ONE dual-use LDS image
+// (mfma.h img_off): S and dP read it by rows, dV and dK read the same bytes
+// transposed with ds_read_b64_tr_b16.  The images and the tile's lse/delta
+// are filled by LDS-DMA, which needs no staging registers, so tile t+1 is in
+// flight into the other buffer while tile t is computed.  The GQA g-loop and
+// the q-tile loop run as one flattened tile sequence: the pipeline is primed
+// once per block, not once per g.
 // ---------------------------------------------------------------------------
 template <int D, bool MASKED = false>
 __global__ __launch_bounds__(FB2_BLOCK, 1) void flash_bwd2_dkv_kernel(
@@ -264,36 +264,25 @@ __global__ __launch_bounds__(FB2_BLOCK, 1) void flash_bwd2_dkv_kernel(
     ushort_t* __restrict__ dk, ushort_t* __restrict__ dv,
     const int* __restrict__ startend,
     int B, int Sq, int Skv, int Hq, int Hk, float scale, int causal) {
+    static_assert(D == 128, "the dual-use image is laid out for 128-column tiles");
     constexpr int BLKQ = 64;               // q tile
     constexpr int DSTEPS = D / 16;
     constexpr int NDT = D / 32;
     constexpr int BLKKV = FB2_WAVES * 32;  // 256 kv rows per block
 
-    // double-buffered q-side tiles (one barrier per q tile)
-    __shared__ ushort_t q_lds[2][BLKQ * D];     // row-major [q][d]
-    __shared__ ushort_t do_lds[2][BLKQ * D];    // row-major [q][d]
-    __shared__ ushort_t qt_lds[2][D * BLKQ];    // transposed [d][q]
-    __shared__ ushort_t dot_lds[2][D * BLKQ];   // transposed [d][q]
-    __shared__ float lse_lds[2][BLKQ];
-    __shared__ float dl_lds[2][BLKQ];
+    // [buffer][0 = Q, 1 = dO] dual-use images, [buffer][0 = lse, 1 = delta]
+    __shared__ __attribute__((aligned(16))) ushort_t qd_lds[2][2][BLKQ * D];
+    __shared__ float ld_lds[2][2][BLKQ];
 
     const int tid = threadIdx.x;
-    const int wave = tid >> 6;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lane = tid & 63;
     const int l32 = lane & 31;
     const int hi = lane >> 5;
 
-    // XCD-aware remap: one (b,h)'s kv-tiles per XCD (shared Q/dO reuse)
+    // heaviest kv tiles first (see mfma.h xcd_grouped_tile)
     int kvt, bh;
-    if ((gridDim.y & 7) == 0) {
-        const int flat = blockIdx.x + gridDim.x * blockIdx.y;
-        const int idx = flat >> 3;
-        kvt = idx % gridDim.x;
-        bh = (flat & 7) * (gridDim.y >> 3) + idx / gridDim.x;
-    } else {
-        kvt = blockIdx.x;
-        bh = blockIdx.y;
-    }
+    xcd_grouped_tile<FA_ORDER_W, true>(kvt, bh);
     const int b = bh / Hk, hk = bh % Hk;
     const int G = Hq / Hk;
     const int kv_base = kvt * BLKKV;
@@ -301,13 +290,12 @@ __global__ __launch_bounds__(FB2_BLOCK, 1) void flash_bwd2_dkv_kernel(
     const int kvg_lane = kvw + l32;          // lane's kv column
     const int causal_off = Skv - Sq;
     // FlashMask: lane owns one kv column -> one bound scalar; the
-    // wave-max bound drives whole-q-tile skipping and the BLOCK max
-    // (published through LDS before the first barrier) lets the whole
-    // workgroup skip staging q tiles no kv row can see
+    // wave-max bound drives whole-q-tile skipping and the BLOCK max ends
+    // the tile sequence of every g: q tiles wholly past it are invisible
+    // to every kv row in the block and are neither staged nor computed
     __shared__ int blk_max_lds[MASKED ? FB2_WAVES : 1];
     int kv_end_lane = 0x7fffffff;
     int wave_max_end = 0x7fffffff;
-    int block_max_end = 0x7fffffff;
     if (MASKED) {
         kv_end_lane = (kvg_lane < Skv)
             ? startend[(long long)b * Skv + kvg_lane] : 0;
@@ -316,6 +304,7 @@ __global__ __launch_bounds__(FB2_BLOCK, 1) void flash_bwd2_dkv_kernel(
         for (int off = 32; off; off >>= 1)
             wave_max_end = max(wave_max_end,
                                __shfl_xor(wave_max_end, off, 64));
+        wave_max_end = __builtin_amdgcn_readfirstlane(wave_max_end);
         if (lane == 0) blk_max_lds[wave] = wave_max_end;
     }
 
@@ -324,7 +313,8 @@ __global__ __launch_bounds__(FB2_BLOCK, 1) void flash_bwd2_dkv_kernel(
     const ushort_t* k_ptr = k + ((long long)b * Skv * Hk + hk) * D;
     const ushort_t* v_ptr = v + ((long long)b * Skv * Hk + hk) * D;
 
-    // stationary per-lane: K^T and V^T B-fragments (one kv row each)
+    // stationary per-lane: K^T and V^T B-fragments (one kv row each).
+    // Ordinary global loads: they retire before the first DMA is issued.
     frag8 bk[DSTEPS], bv[DSTEPS];
     if (kvg_lane < Skv) {
 #pragma unroll
@@ -345,150 +335,142 @@ __global__ __launch_bounds__(FB2_BLOCK, 1) void flash_bwd2_dkv_kernel(
 #pragma unroll
         for (int r = 0; r < 16; r++) { acc_dk[n][r] = 0.f; acc_dv[n][r] = 0.f; }
 
-    // q tiles: under causal only q >= kv_base - off contribute
+    // q tiles [qt0, qt_end) of each g: under causal only q >= kv_base - off
+    // contribute
     int qt0 = 0;
     if (causal) qt0 = max(0, (kv_base - causal_off) / BLKQ);
-    const int n_q_tiles = (Sq + BLKQ - 1) / BLKQ;
-
-    const int s_rowp = tid >> 4;
-    const int s_col = (tid & 15) * 8;
-    const int s_row0 = s_rowp * 2;
-    short8v sq0, sq1, sd0, sd1;
-
-    for (int g = 0; g < G; g++) {
-        const int hq = hk * G + g;
-        const ushort_t* q_ptr = q + ((long long)b * Sq * Hq + hq) * D;
-        const ushort_t* do_ptr = dout + ((long long)b * Sq * Hq + hq) * D;
-        const float* lse_row = lse + ((long long)b * Hq + hq) * Sq;
-        const float* dl_row = delta + ((long long)b * Hq + hq) * Sq;
-
-        auto load_qtile = [&](int q_tb) {
-            int g0 = q_tb + s_row0;
-            sq0 = short8v{0,0,0,0,0,0,0,0}; sq1 = sq0; sd0 = sq0; sd1 = sq0;
-            if (g0 < Sq) {
-                sq0 = *reinterpret_cast<const short8v*>(q_ptr + (long long)g0 * q_row_stride + s_col);
-                sd0 = *reinterpret_cast<const short8v*>(do_ptr + (long long)g0 * q_row_stride + s_col);
-            }
-            if (g0 + 1 < Sq) {
-                sq1 = *reinterpret_cast<const short8v*>(q_ptr + (long long)(g0 + 1) * q_row_stride + s_col);
-                sd1 = *reinterpret_cast<const short8v*>(do_ptr + (long long)(g0 + 1) * q_row_stride + s_col);
-            }
-        };
-        auto write_qtile = [&](int q_tb, int buf) {
-            *reinterpret_cast<short8v*>(swz<D>(q_lds[buf], s_row0, s_col)) = sq0;
-            *reinterpret_cast<short8v*>(swz<D>(q_lds[buf], s_row0 + 1, s_col)) = sq1;
-            *reinterpret_cast<short8v*>(swz<D>(do_lds[buf], s_row0, s_col)) = sd0;
-            *reinterpret_cast<short8v*>(swz<D>(do_lds[buf], s_row0 + 1, s_col)) = sd1;
-#pragma unroll
-            for (int j = 0; j < 8; j++) {
-                unsigned pq = ((unsigned)(unsigned short)sq0[j]) |
-                              (((unsigned)(unsigned short)sq1[j]) << 16);
-                unsigned pd = ((unsigned)(unsigned short)sd0[j]) |
-                              (((unsigned)(unsigned short)sd1[j]) << 16);
-                *reinterpret_cast<unsigned*>(swz<BLKQ>(qt_lds[buf], s_col + j, s_row0)) = pq;
-                *reinterpret_cast<unsigned*>(swz<BLKQ>(dot_lds[buf], s_col + j, s_row0)) = pd;
-            }
-            if (tid < BLKQ) {
-                int qgl = q_tb + tid;
-                lse_lds[buf][tid] = (qgl < Sq) ? lse_row[qgl] : INFINITY;
-                dl_lds[buf][tid] = (qgl < Sq) ? dl_row[qgl] : 0.f;
-            }
-        };
-
-        load_qtile(qt0 * BLKQ);
-        write_qtile(qt0 * BLKQ, qt0 & 1);
+    int qt_end = (Sq + BLKQ - 1) / BLKQ;
+    if (MASKED) {
         __syncthreads();
-        if (MASKED) {
-            // block max of the per-wave bounds (published above): q tiles
-            // wholly past it are invisible to EVERY kv row in the block
-            block_max_end = blk_max_lds[0];
+        int block_max_end = blk_max_lds[0];
 #pragma unroll
-            for (int w = 1; w < FB2_WAVES; w++)
-                block_max_end = max(block_max_end, blk_max_lds[w]);
+        for (int w = 1; w < FB2_WAVES; w++)
+            block_max_end = max(block_max_end, blk_max_lds[w]);
+        block_max_end = __builtin_amdgcn_readfirstlane(block_max_end);
+        if (block_max_end < Sq)
+            qt_end = (max(block_max_end, 0) + BLKQ - 1) / BLKQ;
+    }
+    const int n_tiles = G * max(qt_end - qt0, 0);   // flattened (g, qt)
+
+    // DMA of tile (g, qt) into buffer buf: each wave fills image rows
+    // 8*wave .. +7 of Q and of dO (2 x 1 KiB each; waves 0/1: plus
+    // lse/delta).  A ragged tile cannot be zero-filled by DMA: rows past Sq
+    // re-read row Sq-1 (finite data) and the qgl < Sq visibility test zeroes
+    // their P and dS.
+    auto issue_tile = [&](int g, int qt, int buf) {
+        const int hq = hk * G + g;
+        const long long head_off = ((long long)b * Sq * Hq + hq) * D;
+        const int q_tb = qt * BLKQ;
+        // the kernel sits at the register cap: recompute the per-lane source
+        // offsets every tile (a few VALU ops) rather than let the compiler
+        // hoist them out of the tile loop and spill them, since a scratch
+        // reload after the DMA issue waits vmcnt(0) and drains the prefetch
+        const int ln = fresh_lane_id();
+#pragma unroll
+        for (int i = 0; i < 2; i++) {
+            const int piece = wave * 2 + i;
+            const int src_row = min(q_tb + img_fill_row(piece, ln), Sq - 1);
+            const long long src = head_off + (long long)src_row * q_row_stride +
+                                  img_fill_chunk(piece, ln) * 8;
+            lds_dma16(q + src, &qd_lds[buf][0][piece * 512]);
+            lds_dma16(dout + src, &qd_lds[buf][1][piece * 512]);
         }
+        if (wave < 2) {
+            const float* row = (wave == 0 ? lse : delta) +
+                               ((long long)b * Hq + hq) * Sq;
+            lds_dma4(row + min(q_tb + ln, Sq - 1), &ld_lds[buf][wave][0]);
+        }
+    };
 
-        for (int qt = qt0; qt < n_q_tiles; qt++) {
-            const int q_tb = qt * BLKQ;
-            const int cur = qt & 1;
-            // skip q tiles fully below this wave's causal diagonal, or
-            // (FlashMask) entirely past every bound this wave holds
-            bool wave_skip =
-                causal && (q_tb + BLKQ - 1 + causal_off < kvw);
-            if (MASKED && q_tb >= wave_max_end) wave_skip = true;
+    int g_next = 0, qt_next = qt0;   // next tile to stage
+    auto advance_next = [&]() {
+        if (++qt_next == qt_end) { qt_next = qt0; g_next++; }
+    };
+    // retire the K/V fragment loads here: left pending, the compiler waits
+    // for them with a counted vmcnt inside the tile loop, and that count
+    // would also drain the (uncounted) DMA in flight
+#pragma unroll
+    for (int kk = 0; kk < DSTEPS; kk++)
+        asm volatile("" :: "v"(bk[kk]), "v"(bv[kk]));
+    if (n_tiles > 0) { issue_tile(g_next, qt_next, 0); advance_next(); }
 
-            // process the 64-q tile as two 32-q sub-iterations: only one
-            // (S, dP) register pair is live at a time, which keeps the
-            // file at {acc 128 + K/V frags 64 + state 32} and spill-free
-            if (!wave_skip) {
+    int qt = qt0;
+    for (int t = 0; t < n_tiles; t++) {
+        const int cur = t & 1;
+        // tile t has landed (the compiler does not count the DMA, hence the
+        // explicit wait) and every wave is done reading the other buffer,
+        // which tile t+1 now overwrites while tile t is computed
+        lds_dma_wait_all();
+        __syncthreads();
+        if (t + 1 < n_tiles) { issue_tile(g_next, qt_next, cur ^ 1); advance_next(); }
+
+        const int q_tb = qt * BLKQ;
+        const ushort_t* q_img = qd_lds[cur][0];
+        const ushort_t* do_img = qd_lds[cur][1];
+        const int lane_t = fresh_lane_id();   // for the transposed reads
+        // skip q tiles fully below this wave's causal diagonal, or
+        // (FlashMask) entirely past every bound this wave holds.  Wave-
+        // uniform: the transposed reads below need EXEC all ones.
+        bool wave_skip =
+            causal && (q_tb + BLKQ - 1 + causal_off < kvw);
+        if (MASKED && q_tb >= wave_max_end) wave_skip = true;
+
+        // process the 64-q tile as two 32-q sub-iterations: only one
+        // (S, dP) register pair is live at a time
+        if (!wave_skip) {
 #pragma unroll 1
-                for (int sub = 0; sub < 2; sub++) {
-                    f32x16 st, dp;
+            for (int sub = 0; sub < 2; sub++) {
+                f32x16 st, dp;
 #pragma unroll
-                    for (int r = 0; r < 16; r++) { st[r] = 0.f; dp[r] = 0.f; }
-                    __builtin_amdgcn_s_setprio(1);
+                for (int r = 0; r < 16; r++) { st[r] = 0.f; dp[r] = 0.f; }
+                __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-                    for (int kk = 0; kk < DSTEPS; kk++) {
-                        frag8 aqf = *reinterpret_cast<const frag8*>(
-                            swz<D>(q_lds[cur], sub * 32 + l32, kk * 16 + hi * 8));
-                        frag8 adf = *reinterpret_cast<const frag8*>(
-                            swz<D>(do_lds[cur], sub * 32 + l32, kk * 16 + hi * 8));
-                        st = mfma32(aqf, bk[kk], st);
-                        dp = mfma32(adf, bv[kk], dp);
-                    }
-                    __builtin_amdgcn_s_setprio(0);
-
-                    // P = exp(S*scale - lse[q]) overwrites S; dS = P*(dP -
-                    // delta[q])*scale overwrites dP.  Rows are q (wave-
-                    // uniform per reg): lse/delta broadcast from LDS.
-#pragma unroll
-                    for (int r = 0; r < 16; r++) {
-                        int qrow = sub * 32 + crow32(r, hi);
-                        int qgl = q_tb + qrow;
-                        float ls = lse_lds[cur][qrow];
-                        float dl = dl_lds[cur][qrow];
-                        bool vis = (qgl < Sq) && (kvg_lane < Skv) &&
-                                   (!causal || kvg_lane <= qgl + causal_off);
-                        if (MASKED) vis = vis && (qgl < kv_end_lane);
-                        float p = (vis && ls != INFINITY)
-                                      ? __expf(st[r] * scale - ls) : 0.f;
-                        st[r] = p;
-                        dp[r] = p * (dp[r] - dl) * scale;  // dS
-                    }
-
-                    // dV += P^T·dO, dK += dS^T·Q (contract q: the 2
-                    // k-steps of this sub-tile)
-                    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-                    for (int ksl = 0; ksl < 2; ksl++) {
-                        const int ks = sub * 2 + ksl;
-                        frag8 apt = t12_convert(st, ksl * 8);
-                        frag8 ads = t12_convert(dp, ksl * 8);
-#pragma unroll
-                        for (int n = 0; n < NDT; n++) {
-                            frag8 bdo = *reinterpret_cast<const frag8*>(
-                                swz<BLKQ>(dot_lds[cur], n * 32 + l32, ks * 16 + hi * 8));
-                            frag8 bq = *reinterpret_cast<const frag8*>(
-                                swz<BLKQ>(qt_lds[cur], n * 32 + l32, ks * 16 + hi * 8));
-                            acc_dv[n] = mfma32(apt, bdo, acc_dv[n]);
-                            acc_dk[n] = mfma32(ads, bq, acc_dk[n]);
-                        }
-                    }
-                    __builtin_amdgcn_s_setprio(0);
+                for (int kk = 0; kk < DSTEPS; kk++) {
+                    frag8 aqf = img_row_frag(q_img, sub * 32 + l32, kk, hi);
+                    frag8 adf = img_row_frag(do_img, sub * 32 + l32, kk, hi);
+                    st = mfma32(aqf, bk[kk], st);
+                    dp = mfma32(adf, bv[kk], dp);
                 }
-            }
+                __builtin_amdgcn_s_setprio(0);
 
-            if (qt + 1 < n_q_tiles &&
-                !(MASKED && q_tb + BLKQ >= block_max_end)) {
-                // no register prefetch (register file at capacity); the
-                // load+write go straight into the OTHER buffer, so only
-                // one barrier per tile.  FlashMask: q tiles past the
-                // block's max bound skip the staging entirely
-                load_qtile(q_tb + BLKQ);
-                write_qtile(q_tb + BLKQ, cur ^ 1);
+                // P = exp(S*scale - lse[q]) overwrites S; dS = P*(dP -
+                // delta[q])*scale overwrites dP.  Rows are q (wave-
+                // uniform per reg): lse/delta broadcast from LDS.
+#pragma unroll
+                for (int r = 0; r < 16; r++) {
+                    int qrow = sub * 32 + crow32(r, hi);
+                    int qgl = q_tb + qrow;
+                    float ls = ld_lds[cur][0][qrow];
+                    float dl = ld_lds[cur][1][qrow];
+                    bool vis = (qgl < Sq) && (kvg_lane < Skv) &&
+                               (!causal || kvg_lane <= qgl + causal_off);
+                    if (MASKED) vis = vis && (qgl < kv_end_lane);
+                    float p = (vis && ls != INFINITY)
+                                  ? __expf(st[r] * scale - ls) : 0.f;
+                    st[r] = p;
+                    dp[r] = p * (dp[r] - dl) * scale;  // dS
+                }
+
+                // dV += P^T·dO, dK += dS^T·Q (contract q: the 2
+                // k-steps of this sub-tile)
+                __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+                for (int ksl = 0; ksl < 2; ksl++) {
+                    const int ks = sub * 2 + ksl;
+                    frag8 apt = t12_convert(st, ksl * 8);
+                    frag8 ads = t12_convert(dp, ksl * 8);
+#pragma unroll
+                    for (int n = 0; n < NDT; n++) {
+                        frag8 bdo = img_tr_frag(do_img, ks, n, lane_t);
+                        frag8 bq = img_tr_frag(q_img, ks, n, lane_t);
+                        acc_dv[n] = mfma32(apt, bdo, acc_dv[n]);
+                        acc_dk[n] = mfma32(ads, bq, acc_dk[n]);
+                    }
+                }
+                __builtin_amdgcn_s_setprio(0);
             }
-            __syncthreads();
         }
-        __syncthreads();   // before the next g reuses the LDS tiles
+        if (++qt == qt_end) qt = qt0;
     }
 
     // epilogue: acc C-layout [kv][d] (col = d, row = kv within the wave)
@@ -506,6 +488,42 @@ __global__ __launch_bounds__(FB2_BLOCK, 1) void flash_bwd2_dkv_kernel(
     }
 }
 
+// dual-use image probe: one wave fills a 64 x 128 image by LDS-DMA with the
+// source swizzle and returns it as read by the row path and by the
+// transposed path (both must reproduce X exactly).
+__global__ __launch_bounds__(64) void lds_image_probe(
+    const ushort_t* __restrict__ X, ushort_t* __restrict__ out_row,
+    ushort_t* __restrict__ out_tr) {
+    __shared__ __attribute__((aligned(16))) ushort_t img[64 * 128];
+    const int lane = threadIdx.x;
+    const int l32 = lane & 31, hi = lane >> 5;
+#pragma unroll 1
+    for (int piece = 0; piece < 16; piece++)
+        lds_dma16(X + img_fill_row(piece, lane) * 128 + img_fill_chunk(piece, lane) * 8,
+                  &img[piece * 512]);
+    lds_dma_wait_all();
+    __syncthreads();
+    for (int sub = 0; sub < 2; sub++)
+        for (int kk = 0; kk < 8; kk++) {
+            frag8 f = img_row_frag(img, sub * 32 + l32, kk, hi);
+            *reinterpret_cast<frag8*>(
+                out_row + (sub * 32 + l32) * 128 + kk * 16 + hi * 8) = f;
+        }
+    for (int ks = 0; ks < 4; ks++)
+        for (int n = 0; n < 4; n++) {
+            frag8 f = img_tr_frag(img, ks, n, lane);
+#pragma unroll
+            for (int j = 0; j < 8; j++)
+                out_tr[(ks * 16 + hi * 8 + j) * 128 + n * 32 + l32] = (ushort_t)f[j];
+        }
+}
+
+void launch_lds_image_probe(const void* X, void* out_row, void* out_tr,
+                            hipStream_t stream) {
+    hipLaunchKernelGGL(lds_image_probe, dim3(1), dim3(64), 0, stream,
+                       (const ushort_t*)X, (ushort_t*)out_row, (ushort_t*)out_tr);
+}
+
 // ---------------------------------------------------------------------------
 // launcher
 // ---------------------------------------------------------------------------
@@ -513,21 +531,26 @@ bool launch_flash_bwd2(const void* dout, const void* q, const void* k, const voi
                        const void* o, const float* lse, float* delta,
                        void* dq, void* dk, void* dv,
                        int B, int Sq, int Skv, int Hq, int Hk, int D,
-                       float scale, bool causal, hipStream_t stream) {
+                       float scale, bool causal, hipStream_t stream, int parts) {
     if (D != 128 || (Hq % Hk) != 0) return false;
-    launch_flash_bwd_delta(dout, o, delta, B, Sq, Hq, D, stream);
-    dim3 gq((Sq + 255) / 256, B * Hq);
-    hipLaunchKernelGGL((flash_bwd2_dq_kernel<128, false>), gq, dim3(FB2_BLOCK), 0, stream,
-                       (const ushort_t*)q, (const ushort_t*)k, (const ushort_t*)v,
-                       (const ushort_t*)dout, lse, delta, (ushort_t*)dq,
-                       (const int*)nullptr,
-                       B, Sq, Skv, Hq, Hk, scale, causal ? 1 : 0);
-    dim3 gkv((Skv + 255) / 256, B * Hk);
-    hipLaunchKernelGGL((flash_bwd2_dkv_kernel<128, false>), gkv, dim3(FB2_BLOCK), 0, stream,
-                       (const ushort_t*)q, (const ushort_t*)k, (const ushort_t*)v,
-                       (const ushort_t*)dout, lse, delta, (ushort_t*)dk, (ushort_t*)dv,
-                       (const int*)nullptr,
-                       B, Sq, Skv, Hq, Hk, scale, causal ? 1 : 0);
+    if (parts & FLASH_BWD_DELTA)
+        launch_flash_bwd_delta(dout, o, delta, B, Sq, Hq, D, stream);
+    if (parts & FLASH_BWD_DQ) {
+        dim3 gq((Sq + 255) / 256, B * Hq);
+        hipLaunchKernelGGL((flash_bwd2_dq_kernel<128, false>), gq, dim3(FB2_BLOCK), 0, stream,
+                           (const ushort_t*)q, (const ushort_t*)k, (const ushort_t*)v,
+                           (const ushort_t*)dout, lse, delta, (ushort_t*)dq,
+                           (const int*)nullptr,
+                           B, Sq, Skv, Hq, Hk, scale, causal ? 1 : 0);
+    }
+    if (parts & FLASH_BWD_DKV) {
+        dim3 gkv((Skv + 255) / 256, B * Hk);
+        hipLaunchKernelGGL((flash_bwd2_dkv_kernel<128, false>), gkv, dim3(FB2_BLOCK), 0, stream,
+                           (const ushort_t*)q, (const ushort_t*)k, (const ushort_t*)v,
+                           (const ushort_t*)dout, lse, delta, (ushort_t*)dk, (ushort_t*)dv,
+                           (const int*)nullptr,
+                           B, Sq, Skv, Hq, Hk, scale, causal ? 1 : 0);
+    }
     return true;
 }
 

@@ -77,6 +77,9 @@ void launch_flash_bwd_delta(const void* dout, const void* o, float* delta,
 // Return false (nothing launched) when the shape is not theirs. ----
 void launch_mfma32_probe(const void* A, const void* B, float* C, hipStream_t stream);
 void launch_permlane_probe(int* out0, int* out1, hipStream_t stream);
+// X, out_row, out_tr: 64 x 128 bf16 (see mfma.h dual-use image)
+void launch_lds_image_probe(const void* X, void* out_row, void* out_tr,
+                            hipStream_t stream);
 bool launch_flash_fwd2(const void* q, const void* k, const void* v, void* o,
                        float* lse, int B, int Sq, int Skv, int Hq, int Hk,
                        int D, float scale, bool causal, hipStream_t stream);
@@ -84,11 +87,15 @@ bool launch_flash_fwd2_mask(const void* q, const void* k, const void* v,
                             void* o, float* lse, const int* startend,
                             int B, int Sq, int Skv, int Hq, int Hk,
                             int D, float scale, hipStream_t stream);
+// parts: which of the three backward launches to issue (tools/bench_fa.py
+// times dq and dkv on their own; everything else takes all three)
+enum { FLASH_BWD_DELTA = 1, FLASH_BWD_DQ = 2, FLASH_BWD_DKV = 4, FLASH_BWD_ALL = 7 };
 bool launch_flash_bwd2(const void* dout, const void* q, const void* k, const void* v,
                        const void* o, const float* lse, float* delta,
                        void* dq, void* dk, void* dv,
                        int B, int Sq, int Skv, int Hq, int Hk, int D,
-                       float scale, bool causal, hipStream_t stream);
+                       float scale, bool causal, hipStream_t stream,
+                       int parts = FLASH_BWD_ALL);
 bool launch_flash_bwd2_mask(const void* dout, const void* q, const void* k,
                             const void* v, const void* o, const float* lse,
                             float* delta, void* dq, void* dk, void* dv,

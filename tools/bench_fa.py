@@ -2,11 +2,15 @@
 
 Guide rule #13: cross-run/cross-box deltas under 10% are noise — kernels
 must be timed interleaved in ONE process on ONE box.
+
+The v2 forward, dq and dkv kernels are reported separately (the backward
+binding flash_attn_bwd2_parts launches a chosen subset), next to the v1
+forward and combined backward.  A kernel variant under development goes into
+KERNELS as one more row, so it is timed in the same interleaved loop.
 """
 import argparse
 import sys
 import os
-import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -14,29 +18,49 @@ import torch
 
 from paddlenlp_amd.ops.functional import _load_extension
 
-# name -> force_v1: the default path (v2 8-wave 32x32 kernels at D=128) against
-# the v1 4-wave 16x16 fallback
-KERNELS = {"v2-32x32": False, "v1-linear": True}
+BWD_DELTA, BWD_DQ, BWD_DKV = 1, 2, 4
+
+# matmul counts: fwd 2 (S, PV); dq 3 (S, dP, dQ); dkv 4 (S, dP, dV, dK); the
+# v1 combined backward recomputes S and dP once per kernel like v2 (7)
+# name -> (matmuls, fn(C, t)) with t the dict of tensors built in main()
+KERNELS = {
+    "fwd v2-32x32": (2, lambda C, t: C.flash_attn_fwd_ex(t["q"], t["k"], t["v"], True, False)),
+    "fwd v1-linear": (2, lambda C, t: C.flash_attn_fwd_ex(t["q"], t["k"], t["v"], True, True)),
+    "dq  v2-32x32": (3, lambda C, t: C.flash_attn_bwd2_parts(
+        t["do"], t["q"], t["k"], t["v"], t["o"], t["lse"], t["delta"], True, BWD_DQ)),
+    "dkv v2-32x32": (4, lambda C, t: C.flash_attn_bwd2_parts(
+        t["do"], t["q"], t["k"], t["v"], t["o"], t["lse"], t["delta"], True, BWD_DKV)),
+    "bwd v2-32x32": (7, lambda C, t: C.flash_attn_bwd_ex(
+        t["do"], t["q"], t["k"], t["v"], t["o"], t["lse"], True, False)),
+    "bwd v1-linear": (7, lambda C, t: C.flash_attn_bwd_ex(
+        t["do"], t["q"], t["k"], t["v"], t["o"], t["lse"], True, True)),
+}
 
 
-def _time_interleaved(fn, reps):
-    """Per-kernel wall times with the kernels alternating inside each rep."""
+def _time_interleaved(C, t, reps):
+    """Per-kernel device times (ms) with the kernels alternating inside each rep."""
     results = {name: [] for name in KERNELS}
+    for _, fn in KERNELS.values():   # warm-up
+        fn(C, t)
+    torch.cuda.synchronize()
     for _ in range(reps):
-        for name, force_v1 in KERNELS.items():
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            fn(force_v1)
-            torch.cuda.synchronize()
-            results[name].append(time.perf_counter() - t0)
+        for name, (_, fn) in KERNELS.items():
+            e0 = torch.cuda.Event(enable_timing=True)
+            e1 = torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn(C, t)
+            e1.record()
+            e1.synchronize()
+            results[name].append(e0.elapsed_time(e1))
     return results
 
 
-def _report(tag, results, flops):
+def _report(results, matmul_flops):
     for name, times in results.items():
         ts = sorted(times)[1:-1] or times  # trim outliers
         mean = sum(ts) / len(ts)
-        print(f"  {tag} {name:<9}: {mean*1e3:8.2f} ms  {flops/mean/1e12:7.1f} TF/s")
+        flops = KERNELS[name][0] * matmul_flops
+        print(f"  {name:<14}: {mean:8.3f} ms  {flops/mean/1e9:7.1f} TF/s")
 
 
 def main():
@@ -56,8 +80,8 @@ def main():
     k = torch.randn(args.B, args.S, args.Hk, args.D, device=dev, dtype=torch.bfloat16)
     v = torch.randn(args.B, args.S, args.Hk, args.D, device=dev, dtype=torch.bfloat16)
 
-    # causal attention matmul FLOPs (0.5 visibility): 2 matmuls x 2 flops
-    flops = 0.5 * 2 * 2 * args.B * args.Hq * args.S * args.S * args.D
+    # one causal attention matmul (0.5 visibility), 2 flops per MAC
+    matmul_flops = 0.5 * 2 * args.B * args.Hq * args.S * args.S * args.D
 
     # correctness cross-check first: v2 against v1
     ref_o, ref_lse = C.flash_attn_fwd_ex(q, k, v, True, True)
@@ -66,20 +90,20 @@ def main():
     print(f"  fwd v2 vs v1 max err: {err:.4f}")
     assert err < 3e-2, err
 
-    print(f"shape B{args.B} S{args.S} Hq{args.Hq} Hk{args.Hk} D{args.D}, {args.reps} reps:")
-    _report("fwd", _time_interleaved(
-        lambda force_v1: C.flash_attn_fwd_ex(q, k, v, True, force_v1), args.reps), flops)
-
     do = torch.randn_like(o)
     ref_dq, ref_dk, ref_dv = C.flash_attn_bwd_ex(do, q, k, v, o, lse, True, True)
     dq2, dk2, dv2 = C.flash_attn_bwd_ex(do, q, k, v, o, lse, True, False)
     for nm, a, b in (("dq", ref_dq, dq2), ("dk", ref_dk, dk2), ("dv", ref_dv, dv2)):
         err = (a.float() - b.float()).abs().max().item()
         print(f"  bwd v2 vs v1 {nm} max err: {err:.4f}")
-    bwd_flops = flops * 3.5  # 7 matmuls vs fwd's 2
-    _report("bwd", _time_interleaved(
-        lambda force_v1: C.flash_attn_bwd_ex(do, q, k, v, o, lse, True, force_v1),
-        args.reps), bwd_flops)
+
+    # delta = rowsum(dO * O) as [B, Hq, S] for the dq/dkv-only launches
+    delta = (do.float() * o.float()).sum(-1).permute(0, 2, 1).contiguous()
+    t = dict(q=q, k=k, v=v, o=o, lse=lse, do=do, delta=delta)
+
+    print(f"shape B{args.B} S{args.S} Hq{args.Hq} Hk{args.Hk} D{args.D}, {args.reps} reps:")
+    _report(_time_interleaved(C, t, args.reps), matmul_flops)
+
 
 if __name__ == "__main__":
     main()
