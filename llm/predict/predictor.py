@@ -48,6 +48,9 @@ class PredictorArgument:
     quant_type: str = field(default="")  # "" | "fp8" | "weight_only_int8"
     use_hipgraph: bool = field(default=False)  # capture decode in a hipGraph
     cachekv_int8: bool = field(default=False)  # int8 paged KV (2x capacity)
+    # block-attn engine: run prompts as chunks of at most this many tokens
+    # (engine.extend over the cache); 0 = one-shot prefill
+    prefill_chunk_size: int = field(default=0)
     # speculative decoding: local path of a small draft model (dygraph mode)
     speculate_model: str = field(default="")
     speculate_gamma: int = field(default=4)
@@ -271,7 +274,9 @@ class BlockInferencePredictor(BasePredictor):
                 slots = [s for s in slots if s not in new_slots]
             if not slots:
                 if ins:
-                    logits = self.engine.prefill(ins[1], ins[3], ins[2])
+                    logits = self.engine.prefill(
+                        ins[1], ins[3], ins[2],
+                        chunk_size=cfg.prefill_chunk_size or None)
                     finish_inserts(ins, logits)
                 elif pending:
                     raise RuntimeError(
@@ -291,7 +296,8 @@ class BlockInferencePredictor(BasePredictor):
                 # admit concurrently: the prefill overlaps this decode step
                 # on a side stream (engine.mixed_step) instead of stalling it
                 logits, p_logits = self.engine.mixed_step(
-                    input_ids, bt, lens_before, ins[1], ins[3], ins[2])
+                    input_ids, bt, lens_before, ins[1], ins[3], ins[2],
+                    prefill_chunk_size=cfg.prefill_chunk_size or None)
             else:
                 logits = self.decode_fn(input_ids, bt, lens_before)
                 p_logits = None

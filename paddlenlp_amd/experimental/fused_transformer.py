@@ -53,6 +53,32 @@ class FusedMultiTransformerConfig:
 # ---------------------------------------------------------------------------
 # CPU reference versions of the paged kernels (test oracle)
 # ---------------------------------------------------------------------------
+def _gather_paged_kv(k_cache, v_cache, blocks, L, D, k_scale=None, v_scale=None):
+    """First L cache positions of one sequence as fp32 k, v [L, Hk, D]
+    (int8 / packed-int4 caches dequantised with the per-(token, head)
+    scales)."""
+    Hk = k_cache.shape[2]
+
+    def _unpack4(t):
+        # packed uint8 nibbles (offset-binary q+8) -> float
+        hi = (t >> 4).to(torch.int8) - 8
+        lo = (t & 0xF).to(torch.int8) - 8
+        return torch.stack([hi, lo], dim=-1).reshape(*t.shape[:-1], D).float()
+
+    if k_cache.dtype == torch.uint8:
+        k = _unpack4(k_cache[blocks]).reshape(-1, Hk, D)[:L]
+        v = _unpack4(v_cache[blocks]).reshape(-1, Hk, D)[:L]
+    else:
+        k = k_cache[blocks].reshape(-1, Hk, D)[:L].float()  # [L, Hk, D]
+        v = v_cache[blocks].reshape(-1, Hk, D)[:L].float()
+    if k_scale is not None:
+        ks = k_scale[blocks].reshape(-1, Hk)[:L].float()
+        vs = v_scale[blocks].reshape(-1, Hk)[:L].float()
+        k = k * ks[:, :, None]
+        v = v * vs[:, :, None]
+    return k, v
+
+
 def paged_decode_attn_ref(q, k_cache, v_cache, block_table, seq_lens,
                           k_scale=None, v_scale=None):
     """q [B, Hq, D] -> out [B, Hq, D] (fp32 math; int8 caches dequant with
@@ -61,29 +87,11 @@ def paged_decode_attn_ref(q, k_cache, v_cache, block_table, seq_lens,
     bs = k_cache.shape[1]
     Hk = k_cache.shape[2]
     out = torch.empty_like(q)
-
-    def _unpack4(t):
-        # packed uint8 nibbles (offset-binary q+8) -> float
-        hi = (t >> 4).to(torch.int8) - 8
-        lo = (t & 0xF).to(torch.int8) - 8
-        return torch.stack([hi, lo], dim=-1).reshape(*t.shape[:-1], D).float()
-
-    is_int4 = k_cache.dtype == torch.uint8
     for b in range(B):
         L = int(seq_lens[b])
         nb = (L + bs - 1) // bs
         blocks = block_table[b, :nb].long()
-        if is_int4:
-            k = _unpack4(k_cache[blocks]).reshape(-1, Hk, D)[:L]
-            v = _unpack4(v_cache[blocks]).reshape(-1, Hk, D)[:L]
-        else:
-            k = k_cache[blocks].reshape(-1, Hk, D)[:L].float()  # [L, Hk, D]
-            v = v_cache[blocks].reshape(-1, Hk, D)[:L].float()
-        if k_scale is not None:
-            ks = k_scale[blocks].reshape(-1, Hk)[:L].float()
-            vs = v_scale[blocks].reshape(-1, Hk)[:L].float()
-            k = k * ks[:, :, None]
-            v = v * vs[:, :, None]
+        k, v = _gather_paged_kv(k_cache, v_cache, blocks, L, D, k_scale, v_scale)
         rep = Hq // Hk
         k = k.repeat_interleave(rep, dim=1)
         v = v.repeat_interleave(rep, dim=1)
@@ -91,6 +99,36 @@ def paged_decode_attn_ref(q, k_cache, v_cache, block_table, seq_lens,
         s = torch.einsum("hd,lhd->hl", qb, k) / math.sqrt(D)
         p = s.softmax(-1)
         out[b] = torch.einsum("hl,lhd->hd", p, v).to(q.dtype)
+    return out
+
+
+def paged_append_attn_ref(q, k_cache, v_cache, block_table, seq_lens_before,
+                          token_counts=None, k_scale=None, v_scale=None):
+    """q [B, T, Hq, D] (roped; the cache already holds the new tokens) ->
+    out [B, T, Hq, D].  Token t of sequence b sits at seq_lens_before[b] + t
+    and attends to cache positions 0..that; rows at or past token_counts[b]
+    are zero.  fp32 math, same dequant rules as paged_decode_attn_ref."""
+    B, T, Hq, D = q.shape
+    bs = k_cache.shape[1]
+    Hk = k_cache.shape[2]
+    out = torch.zeros_like(q)
+    for b in range(B):
+        n = T if token_counts is None else min(max(int(token_counts[b]), 0), T)
+        if n == 0:
+            continue
+        before = int(seq_lens_before[b])
+        L = before + n
+        nb = (L + bs - 1) // bs
+        blocks = block_table[b, :nb].long()
+        k, v = _gather_paged_kv(k_cache, v_cache, blocks, L, D, k_scale, v_scale)
+        rep = Hq // Hk
+        k = k.repeat_interleave(rep, dim=1)
+        v = v.repeat_interleave(rep, dim=1)
+        s = torch.einsum("thd,lhd->htl", q[b, :n].float(), k) / math.sqrt(D)
+        pos = before + torch.arange(n, device=q.device)
+        hidden = torch.arange(L, device=q.device)[None, :] > pos[:, None]
+        p = s.masked_fill(hidden[None], float("-inf")).softmax(-1)
+        out[b, :n] = torch.einsum("htl,lhd->thd", p, v).to(q.dtype)
     return out
 
 
@@ -523,7 +561,90 @@ class FusedMultiTransformer(nn.Module):
             self.k_scales[i] if self.k_scales is not None else None,
             self.v_scales[i] if self.v_scales is not None else None)
 
+    def _paged_append_attn(self, i, q, block_table, lens_before, token_counts=None):
+        """q [B, T, Hq, D] over the cache that already holds the T new
+        tokens -> [B, T, Hq, D]; rows at or past token_counts are zero."""
+        ks = self.k_scales[i] if self.k_scales is not None else None
+        vs = self.v_scales[i] if self.v_scales is not None else None
+        if not q.is_cuda:
+            return paged_append_attn_ref(
+                q, self.k_caches[i], self.v_caches[i], block_table, lens_before,
+                token_counts, ks, vs)
+        from ..ops.functional import _load_extension
+
+        C = _load_extension()
+        B, T, Hq, D = q.shape
+        if D == 128 and Hq // self.config.num_kv_heads <= 16:
+            return C.paged_append_attn(
+                q, self.k_caches[i], self.v_caches[i], block_table, lens_before,
+                token_counts, ks, vs)
+        # shapes the append kernel does not take (D = 64, larger groups): one
+        # decode-kernel pass per token.  That kernel leaves `out` untouched
+        # for seq_len <= 0, so rows past token_counts are masked explicitly.
+        if token_counts is None:
+            token_counts = torch.full_like(lens_before, T)
+        out = torch.zeros_like(q)
+        for t in range(T):
+            live = token_counts > t
+            lens_t = torch.where(live, lens_before + (t + 1), torch.zeros_like(lens_before))
+            o = C.paged_decode_attn(
+                q[:, t].contiguous(), self.k_caches[i], self.v_caches[i],
+                block_table, lens_t, ks, vs)
+            out[:, t] = torch.where(live[:, None, None], o, torch.zeros_like(o))
+        return out
+
+    def _ffn(self, x, i):
+        c = self.config
+        h = self._rms(x, self.ffn_ln_scales[i])
+        if c.moe_num_experts > 0:
+            return x + self._tp_reduce(self._moe_ffn(h, i))
+        gu = self._mm(h, "gate_up_weights", i)
+        act = ops.swiglu(gu) if gu.is_cuda else reference.swiglu(gu)
+        return x + self._tp_reduce(self._mm(act, "down_weights", i))
+
+    def _logits(self, x):
+        """x [..., H] (final-normed) -> fp32 logits [..., V]."""
+        if "lm_head" in self._qw:
+            from ..quantization import weight_only_linear
+
+            q, sc = self._qw["lm_head"][0]
+            return weight_only_linear(x, q, sc, None, self.quant_algo).float()
+        return (x @ self.lm_head.t()).float()
+
     # ------------------------------------------------------------------
+    @torch.no_grad()
+    def extend(self, input_ids, block_table, seq_lens_before, token_counts=None,
+               all_logits=False) -> torch.Tensor:
+        """T new tokens per sequence on top of what the cache already holds:
+        a prefill chunk, a new chat turn, or a draft to verify.
+
+        input_ids [B, T] (right-padded); seq_lens_before[b] = tokens already
+        cached; token_counts[b] in 0..T = valid tokens of row b (None = T).
+        The caller must have extended the block table for the new tokens.
+        Returns the logits of each sequence's last valid token [B, V], or,
+        with all_logits, of every position [B, T, V] (rows past token_counts
+        are unspecified).  A sequence with token_counts[b] == 0 writes nothing
+        to the cache; its returned row is unspecified but finite."""
+        c = self.config
+        B, T = input_ids.shape
+        x = F.embedding(input_ids, self.embed_tokens)  # [B, T, H]
+        for i in range(c.num_layers):
+            h = self._rms(x, self.ln_scales[i])
+            qkv = self._mm(h, "qkv_weights", i)          # [B, T, qkv_out]
+            if c.qkv_bias:
+                qkv = qkv + self.qkv_biases[i]
+            q = self._rope_append(i, qkv, block_table, seq_lens_before, token_counts)
+            attn = self._paged_append_attn(i, q, block_table, seq_lens_before, token_counts)
+            x = x + self._tp_reduce(self._mm(attn.reshape(B, T, -1), "out_proj_weights", i))
+            x = self._ffn(x, i)
+        x = self._rms(x, self.final_norm)
+        if all_logits:
+            return self._logits(x)
+        if token_counts is None:
+            return self._logits(x[:, -1])
+        idx = (token_counts.long() - 1).clamp(min=0)
+        return self._logits(x[torch.arange(B, device=x.device), idx])
+
     @torch.no_grad()
     def decode_step(self, input_ids, block_table, seq_lens_before) -> torch.Tensor:
         """One token per sequence.  input_ids [B, 1]; returns logits [B, V].
@@ -542,32 +663,33 @@ class FusedMultiTransformer(nn.Module):
             q = self._rope_append(i, qkv, block_table, seq_lens_before)
             attn = self._paged_attn(i, q[:, 0], block_table, seq_lens_after)
             x = x + self._tp_reduce(self._mm(attn.reshape(B, 1, -1), "out_proj_weights", i))
-            h = self._rms(x, self.ffn_ln_scales[i])
-            if c.moe_num_experts > 0:
-                x = x + self._tp_reduce(self._moe_ffn(h, i))
-            else:
-                gu = self._mm(h, "gate_up_weights", i)
-                act = ops.swiglu(gu) if gu.is_cuda else reference.swiglu(gu)
-                x = x + self._tp_reduce(self._mm(act, "down_weights", i))
+            x = self._ffn(x, i)
         x = self._rms(x, self.final_norm)
-        if "lm_head" in self._qw:
-            from ..quantization import weight_only_linear
-
-            q, sc = self._qw["lm_head"][0]
-            logits = weight_only_linear(x[:, 0], q, sc, None, self.quant_algo)
-        else:
-            logits = x[:, 0] @ self.lm_head.t()
-        return logits.float()
+        return self._logits(x[:, 0])
 
     @torch.no_grad()
-    def prefill(self, input_ids, block_table, prompt_lens) -> torch.Tensor:
+    def prefill(self, input_ids, block_table, prompt_lens, chunk_size=None) -> torch.Tensor:
         """Prefill a batch of prompts (right-padded to a common T).
         input_ids [B, T]; prompt_lens [B]; returns last-token logits [B, V].
 
         Uses the training flash kernel on the contiguous prompt; the fused
-        rope+append kernel back-fills the paged cache in the same pass."""
+        rope+append kernel back-fills the paged cache in the same pass.
+
+        With chunk_size set, the prompt runs instead as consecutive `extend`
+        calls of at most chunk_size tokens over the growing cache; each
+        sequence's logits come from the chunk holding its last token."""
         c = self.config
         B, T = input_ids.shape
+        if chunk_size:
+            logits = None
+            for c0 in range(0, T, chunk_size):
+                n = min(chunk_size, T - c0)
+                before = prompt_lens.clamp(max=c0)
+                counts = (prompt_lens - c0).clamp(min=0, max=n)
+                lg = self.extend(input_ids[:, c0:c0 + n], block_table, before, counts)
+                ends_here = (prompt_lens > c0) & (prompt_lens <= c0 + n)
+                logits = lg if logits is None else torch.where(ends_here[:, None], lg, logits)
+            return logits
         x = F.embedding(input_ids, self.embed_tokens)
         zeros = torch.zeros_like(prompt_lens)
         for i in range(c.num_layers):
@@ -589,31 +711,22 @@ class FusedMultiTransformer(nn.Module):
             else:
                 attn = reference.flash_attention(q, k_roped, v, causal=True)
             x = x + self._tp_reduce(self._mm(attn.reshape(B, T, -1), "out_proj_weights", i))
-            h = self._rms(x, self.ffn_ln_scales[i])
-            if c.moe_num_experts > 0:
-                x = x + self._tp_reduce(self._moe_ffn(h, i))
-            else:
-                gu = self._mm(h, "gate_up_weights", i)
-                act = ops.swiglu(gu) if gu.is_cuda else reference.swiglu(gu)
-                x = x + self._tp_reduce(self._mm(act, "down_weights", i))
+            x = self._ffn(x, i)
         x = self._rms(x, self.final_norm)
         idx = (prompt_lens.long() - 1).clamp(min=0)
         last = x[torch.arange(B, device=x.device), idx]
-        if "lm_head" in self._qw:
-            from ..quantization import weight_only_linear
-
-            q, sc = self._qw["lm_head"][0]
-            return weight_only_linear(last, q, sc, None, self.quant_algo).float()
-        return (last @ self.lm_head.t()).float()
+        return self._logits(last)
 
 
     @torch.no_grad()
     def mixed_step(self, decode_ids, decode_bt, decode_lens,
-                   prefill_ids=None, prefill_bt=None, prefill_lens=None):
+                   prefill_ids=None, prefill_bt=None, prefill_lens=None,
+                   prefill_chunk_size=None):
         """One engine call serving a mixed batch: the running decode batch
         plus a freshly admitted prompt batch.  The reference runs encoder
         and decoder work on dual streams with event hand-off
-        (csrc/gpu/append_attention.cu:120-160); here the prefill runs on a
+        (csrc/gpu/append_attention.cu:120-160); here the prefill (chunked
+        when prefill_chunk_size is set) runs on a
         side HIP stream overlapping the decode pass — weights are
         read-only and the cache blocks are disjoint, so no ordering is
         needed beyond the join.  Continuous batching therefore admits new
@@ -624,14 +737,15 @@ class FusedMultiTransformer(nn.Module):
             return self.decode_step(decode_ids, decode_bt, decode_lens), None
         if not decode_ids.is_cuda:
             d = self.decode_step(decode_ids, decode_bt, decode_lens)
-            p = self.prefill(prefill_ids, prefill_bt, prefill_lens)
+            p = self.prefill(prefill_ids, prefill_bt, prefill_lens, prefill_chunk_size)
             return d, p
         if not hasattr(self, "_side_stream") or self._side_stream is None:
             self._side_stream = torch.cuda.Stream()
         cur = torch.cuda.current_stream()
         self._side_stream.wait_stream(cur)
         with torch.cuda.stream(self._side_stream):
-            p_logits = self.prefill(prefill_ids, prefill_bt, prefill_lens)
+            p_logits = self.prefill(prefill_ids, prefill_bt, prefill_lens,
+                                    prefill_chunk_size)
         d_logits = self.decode_step(decode_ids, decode_bt, decode_lens)
         cur.wait_stream(self._side_stream)
         return d_logits, p_logits

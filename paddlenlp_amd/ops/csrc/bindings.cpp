@@ -454,6 +454,56 @@ torch::Tensor paged_decode_attn(torch::Tensor q, torch::Tensor k_cache, torch::T
     return out;
 }
 
+// T new tokens per sequence over the cache that already holds them
+// (rope_cache_append first).  r_tiles forces the kernel's row tiles per
+// workgroup (tools/bench_append.py); 0 lets the launcher choose.
+torch::Tensor paged_append_attn(torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cache,
+                                torch::Tensor block_table, torch::Tensor seq_lens_before,
+                                c10::optional<torch::Tensor> token_counts,
+                                c10::optional<torch::Tensor> k_scale,
+                                c10::optional<torch::Tensor> v_scale,
+                                int64_t r_tiles) {
+    CHECK_GPU(q); CHECK_CONTIG(q); CHECK_BF16(q);
+    TORCH_CHECK(q.dim() == 4, "q must be [B, T, Hq, D]");
+    int B = q.size(0), T = q.size(1), Hq = q.size(2), D = q.size(3);
+    int block_size = k_cache.size(1), Hk = k_cache.size(2);
+    int max_blocks = block_table.size(1);
+    int cache_mode = 0;
+    if (k_cache.scalar_type() == torch::kChar) cache_mode = 1;
+    else if (k_cache.scalar_type() == torch::kByte) cache_mode = 2;
+    TORCH_CHECK(cache_mode == 0 || (k_scale.has_value() && v_scale.has_value()),
+                "quantized KV cache needs k_scale/v_scale");
+    TORCH_CHECK(block_table.size(0) == B && seq_lens_before.numel() == B,
+                "block_table / seq_lens_before must have one row per sequence");
+    TORCH_CHECK(!token_counts.has_value() || token_counts->numel() == B,
+                "token_counts must be [B]");
+    // zeros: rows at or past token_counts[b] are not written by the kernel
+    auto out = torch::zeros_like(q);
+    if (B == 0 || T == 0) return out;
+    int R = 0, nrg = 0, nsplit = 0;
+    TORCH_CHECK(paged_append_plan(B, T, Hq, Hk, D, (int)r_tiles, &R, &nrg, &nsplit),
+                "paged_append_attn: no kernel for head dim D=", D, " with GQA group G=",
+                Hk > 0 ? Hq / Hk : 0, " (needs D == 128, G <= 16, Hq % Hk == 0)");
+    float scale = 1.0f / std::sqrt((float)D);
+    torch::Tensor partials;
+    float* pptr = nullptr;
+    if (nsplit > 1) {
+        partials = torch::empty({(long)B * Hk * nrg, (long)nsplit, (long)16 * R, (long)(2 + D)},
+                                q.options().dtype(torch::kFloat32));
+        pptr = partials.data_ptr<float>();
+    }
+    bool ok = launch_paged_append_attn(
+        q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+        cache_mode ? k_scale->data_ptr<float>() : nullptr,
+        cache_mode ? v_scale->data_ptr<float>() : nullptr,
+        block_table.data_ptr<int>(), seq_lens_before.data_ptr<int>(),
+        token_counts.has_value() ? token_counts->data_ptr<int>() : nullptr,
+        out.data_ptr(), pptr, (int)r_tiles, B, T, Hq, Hk, D, block_size, max_blocks,
+        scale, cache_mode, cur_stream());
+    TORCH_CHECK(ok, "paged_append_attn: kernel refused D=", D, " G=", Hq / Hk);
+    return out;
+}
+
 torch::Tensor rope_cache_append(torch::Tensor qkv, torch::Tensor k_cache, torch::Tensor v_cache,
                                 torch::Tensor block_table, torch::Tensor seq_lens_before,
                                 torch::Tensor cos_t, torch::Tensor sin_t,
@@ -571,6 +621,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
           py::arg("block_table"), py::arg("seq_lens"),
           py::arg("k_scale") = c10::nullopt, py::arg("v_scale") = c10::nullopt);
+    m.def("paged_append_attn", &paged_append_attn,
+          py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
+          py::arg("block_table"), py::arg("seq_lens_before"),
+          py::arg("token_counts") = c10::nullopt,
+          py::arg("k_scale") = c10::nullopt, py::arg("v_scale") = c10::nullopt,
+          py::arg("r_tiles") = 0);
     m.def("rope_cache_append", &rope_cache_append,
           py::arg("qkv"), py::arg("k_cache"), py::arg("v_cache"),
           py::arg("block_table"), py::arg("seq_lens_before"),

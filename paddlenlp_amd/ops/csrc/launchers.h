@@ -129,6 +129,25 @@ void launch_rope_cache_append(const void* qkv, void* q_out, void* k_cache, void*
                               int max_blocks, const int* token_counts,
                               int cache_mode, hipStream_t stream);
 
+// ---- paged_attn_append.hip: T new tokens per sequence over the cache that
+// already holds them.  q/out are [B, T, Hq, D]; query token t of sequence b
+// sits at seq_lens_before[b] + t and attends to positions 0..that. ----
+// Launch geometry: R = 1 or 2 16-row query tiles per workgroup (r_tiles = 0
+// picks it from the shape), row groups per (b, kv-head) and kv splits.  false
+// when the kernel does not take the shape (D != 128 or GQA group > 16).
+bool paged_append_plan(int B, int T, int Hq, int Hk, int D, int r_tiles,
+                       int* R, int* nrg, int* nsplit);
+// false (nothing launched) for a shape paged_append_plan refuses.  out must
+// be zero-filled: rows at or past token_counts[b] are not written.  partials
+// holds B*Hk*nrg*nsplit*16R*(2+D) floats when nsplit > 1.
+bool launch_paged_append_attn(const void* q, const void* k_cache, const void* v_cache,
+                              const float* k_scale, const float* v_scale,
+                              const int* block_table, const int* seq_lens_before,
+                              const int* token_counts, void* out, float* partials,
+                              int r_tiles, int B, int T, int Hq, int Hk, int D,
+                              int block_size, int max_blocks, float scale,
+                              int cache_mode, hipStream_t stream);
+
 // ---- wint8_gemv.hip / skinny_gemm.hip ----
 void launch_wint8_gemv(const void* x, const void* wq, const float* scale, void* y,
                        int M, int N, int K, hipStream_t stream);

@@ -32,12 +32,7 @@
 //
 // Reference behavior: csrc/gpu/append_attn decode path.
 #include "launchers.h"
-#include "mfma.h"
-
-#define PD3_WAVES 4
-#define PD3_BLOCK (PD3_WAVES * 64)
-#define PD3_TILE 128
-#define PD3_MAXG 16
+#include "paged_kv.h"
 
 // MODE: 0 = bf16 cache, 1 = int8, 2 = int4 packed nibbles (q+8 offset)
 template <int D, int MODE>
@@ -83,11 +78,6 @@ __global__ __launch_bounds__(PD3_BLOCK) void paged_decode_attn3_kernel(
     const int c0 = split * chunk;
     const int c1 = min(seq_len, c0 + chunk);
 
-    const ushort_t* k16 = (const ushort_t*)k_cache;
-    const ushort_t* v16 = (const ushort_t*)v_cache;
-    const signed char* k8 = (const signed char*)k_cache;
-    const signed char* v8 = (const signed char*)v_cache;
-    const unsigned char* k4 = (const unsigned char*)k_cache;
     const int* bt = block_table + (long long)b * max_blocks;
 
     // Q^T B-fragments: lane holds Q[hq0 + l16][kk*32 + lg*8 + j]
@@ -120,32 +110,8 @@ __global__ __launch_bounds__(PD3_BLOCK) void paged_decode_attn3_kernel(
             int tok = t0 + s_r0 + rr;
             bool valid = tok < c1;
             if (valid) {
-                int blk = bt[tok / block_size];
-                long long rec = ((long long)blk * block_size + (tok % block_size)) * Hk + hk;
-                long long base = rec * D + s_c;
-                if (MODE == 1) {
-                    float vs = v_scale[rec];
-#pragma unroll
-                    for (int cc = 0; cc < 4; cc++)
-#pragma unroll
-                        for (int j = 0; j < 8; j++)
-                            vr[rr][cc][j] = (short)f32_to_bf16((float)v8[base + cc * 8 + j] * vs);
-                } else if (MODE == 2) {
-                    float vs = v_scale[rec];
-                    const unsigned char* v4 = (const unsigned char*)v_cache + (rec * D + s_c) / 2;
-#pragma unroll
-                    for (int cc = 0; cc < 4; cc++)
-#pragma unroll
-                        for (int j = 0; j < 4; j++) {
-                            unsigned byte = v4[cc * 4 + j];
-                            vr[rr][cc][j * 2] = (short)f32_to_bf16(((int)(byte >> 4) - 8) * vs);
-                            vr[rr][cc][j * 2 + 1] = (short)f32_to_bf16(((int)(byte & 0xF) - 8) * vs);
-                        }
-                } else {
-#pragma unroll
-                    for (int cc = 0; cc < 4; cc++)
-                        vr[rr][cc] = *reinterpret_cast<const short8v*>(v16 + base + cc * 8);
-                }
+                long long rec = pkv_record(bt, tok, block_size, Hk, hk);
+                pkv_load_v_row<D, MODE>(vr[rr], v_cache, v_scale, rec, s_c);
             } else {
 #pragma unroll
                 for (int cc = 0; cc < 4; cc++)
@@ -153,18 +119,7 @@ __global__ __launch_bounds__(PD3_BLOCK) void paged_decode_attn3_kernel(
             }
         }
     };
-    auto write_tile = [&]() {
-#pragma unroll
-        for (int cc = 0; cc < 4; cc++) {
-#pragma unroll
-            for (int j = 0; j < 8; j++) {
-                unsigned p32 = ((unsigned)(unsigned short)vr[0][cc][j]) |
-                               (((unsigned)(unsigned short)vr[1][cc][j]) << 16);
-                *reinterpret_cast<unsigned*>(
-                    swz<PD3_TILE>(vt_lds, s_c + cc * 8 + j, s_r0)) = p32;
-            }
-        }
-    };
+    auto write_tile = [&]() { pkv_write_vt(vt_lds, vr, s_c, s_r0); };
 
     if (c0 < c1) {
         load_tile(c0);
@@ -186,35 +141,9 @@ __global__ __launch_bounds__(PD3_BLOCK) void paged_decode_attn3_kernel(
             for (int s = 0; s < 2; s++) {
                 int tok = tq0 + s * 16 + l16;
                 int tokc = min(tok, c1 - 1);
-                int blk = bt[tokc / block_size];
-                long long rec = ((long long)blk * block_size + (tokc % block_size)) * Hk + hk;
+                long long rec = pkv_record(bt, tokc, block_size, Hk, hk);
                 frag8 ak[KD];
-                if (MODE == 1) {
-                    float ks = k_scale[rec];
-                    const signed char* kb = k8 + rec * D;
-#pragma unroll
-                    for (int kk = 0; kk < KD; kk++)
-#pragma unroll
-                        for (int j = 0; j < 8; j++)
-                            ak[kk][j] = (short)f32_to_bf16(
-                                (float)kb[kk * 32 + lg * 8 + j] * ks);
-                } else if (MODE == 2) {
-                    float ks = k_scale[rec];
-                    const unsigned char* kb = k4 + rec * D / 2;
-#pragma unroll
-                    for (int kk = 0; kk < KD; kk++)
-#pragma unroll
-                        for (int j = 0; j < 4; j++) {
-                            unsigned byte = kb[(kk * 32 + lg * 8) / 2 + j];
-                            ak[kk][j * 2] = (short)f32_to_bf16(((int)(byte >> 4) - 8) * ks);
-                            ak[kk][j * 2 + 1] = (short)f32_to_bf16(((int)(byte & 0xF) - 8) * ks);
-                        }
-                } else {
-                    const ushort_t* kb = k16 + rec * D;
-#pragma unroll
-                    for (int kk = 0; kk < KD; kk++)
-                        ak[kk] = *reinterpret_cast<const frag8*>(kb + kk * 32 + lg * 8);
-                }
+                pkv_load_k_frags<D, MODE>(ak, k_cache, k_scale, rec, lg);
                 __builtin_amdgcn_s_setprio(1);
 #pragma unroll
                 for (int kk = 0; kk < KD; kk++)
