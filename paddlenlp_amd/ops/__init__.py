@@ -1,5 +1,9 @@
 from .functional import (  # noqa: F401
+    add_rms_norm,
     build_rope_cache,
+    layer_fusion_enabled,
+    packed_rope_attention,
+    packed_rope_attention_supported,
     cross_entropy,
     extension_available,
     flash_attention,

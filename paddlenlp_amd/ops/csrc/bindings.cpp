@@ -15,34 +15,82 @@ static hipStream_t cur_stream() {
 }
 
 // ---------------------------------------------------------------------------
-std::vector<torch::Tensor> rms_norm_fwd(torch::Tensor x, torch::Tensor w, double eps) {
+// delta defined: h = bf16(x + delta), y = rms_norm(h); returns {h, y, invrms}.
+// Otherwise y = rms_norm(x); returns {y, invrms}.
+static std::vector<torch::Tensor> rms_norm_fwd_impl(const torch::Tensor& x,
+                                                    const torch::Tensor* delta,
+                                                    const torch::Tensor& w, double eps) {
     CHECK_GPU(x); CHECK_CONTIG(x); CHECK_BF16(x); CHECK_BF16(w);
     int H = x.size(-1);
     TORCH_CHECK(H % 8 == 0, "hidden size must be a multiple of 8");
+    TORCH_CHECK(w.numel() == H && w.is_contiguous(), "weight must be a contiguous [H] tensor");
     long long rows = x.numel() / H;
     auto y = torch::empty_like(x);
     auto invrms = torch::empty({rows}, x.options().dtype(torch::kFloat32));
-    launch_rms_norm_fwd(x.data_ptr(), w.data_ptr(), y.data_ptr(),
-                        invrms.data_ptr<float>(), rows, H, (float)eps, cur_stream());
-    return {y, invrms};
+    if (!delta) {
+        launch_rms_norm_fwd(x.data_ptr(), nullptr, w.data_ptr(), nullptr, y.data_ptr(),
+                            invrms.data_ptr<float>(), rows, H, (float)eps, cur_stream());
+        return {y, invrms};
+    }
+    CHECK_GPU((*delta)); CHECK_CONTIG((*delta)); CHECK_BF16((*delta));
+    TORCH_CHECK(delta->sizes() == x.sizes(), "residual and delta shapes must agree");
+    auto h = torch::empty_like(x);
+    launch_rms_norm_fwd(x.data_ptr(), delta->data_ptr(), w.data_ptr(), h.data_ptr(),
+                        y.data_ptr(), invrms.data_ptr<float>(), rows, H, (float)eps,
+                        cur_stream());
+    return {h, y, invrms};
+}
+
+// dh defined: dx = bf16(bf16(dx_norm) + dh), the gradient of both addends.
+static std::vector<torch::Tensor> rms_norm_bwd_impl(const torch::Tensor& dy,
+                                                    const torch::Tensor* dh,
+                                                    const torch::Tensor& x,
+                                                    const torch::Tensor& w,
+                                                    const torch::Tensor& invrms) {
+    CHECK_GPU(dy); CHECK_CONTIG(dy); CHECK_BF16(dy);
+    CHECK_GPU(x); CHECK_CONTIG(x); CHECK_BF16(x);
+    TORCH_CHECK(dy.sizes() == x.sizes(), "dy must be shaped like x");
+    int H = x.size(-1);
+    TORCH_CHECK(H % 8 == 0, "hidden size must be a multiple of 8");
+    long long rows = x.numel() / H;
+    TORCH_CHECK(invrms.numel() == rows, "invrms must have one entry per row");
+    if (dh) {
+        CHECK_GPU((*dh)); CHECK_CONTIG((*dh)); CHECK_BF16((*dh));
+        TORCH_CHECK(dh->sizes() == x.sizes(), "dh must be shaped like x");
+    }
+    bool needs_zero = false;
+    int P = rms_norm_bwd_partials(rows, H, &needs_zero);
+    auto dx = torch::empty_like(x);
+    auto f32 = x.options().dtype(torch::kFloat32);
+    auto dw_partial = needs_zero ? torch::zeros({P, H}, f32) : torch::empty({P, H}, f32);
+    bool w_bf16 = w.scalar_type() == torch::kBFloat16;
+    auto dw32 = torch::zeros({H}, f32);
+    auto dw = w_bf16 ? torch::empty_like(w) : dw32;
+    launch_rms_norm_bwd(dy.data_ptr(), x.data_ptr(), dh ? dh->data_ptr() : nullptr,
+                        w.data_ptr(), invrms.data_ptr<float>(), dx.data_ptr(),
+                        dw_partial.data_ptr<float>(), dw32.data_ptr<float>(),
+                        dw.data_ptr(), w_bf16, rows, H, P, cur_stream());
+    return {dx, dw};
+}
+
+std::vector<torch::Tensor> rms_norm_fwd(torch::Tensor x, torch::Tensor w, double eps) {
+    return rms_norm_fwd_impl(x, nullptr, w, eps);
 }
 
 std::vector<torch::Tensor> rms_norm_bwd(torch::Tensor dy, torch::Tensor x, torch::Tensor w,
                                         torch::Tensor invrms) {
-    CHECK_GPU(dy); CHECK_CONTIG(dy); CHECK_BF16(dy);
-    int H = x.size(-1);
-    long long rows = x.numel() / H;
-    int P = (int)std::min<long long>(rows, 2048);
-    auto dx = torch::empty_like(x);
-    auto dw_partial = torch::zeros({P, H}, x.options().dtype(torch::kFloat32));
-    bool w_bf16 = w.scalar_type() == torch::kBFloat16;
-    auto dw32 = torch::zeros({H}, x.options().dtype(torch::kFloat32));
-    auto dw = w_bf16 ? torch::empty_like(w) : dw32;
-    launch_rms_norm_bwd(dy.data_ptr(), x.data_ptr(), w.data_ptr(),
-                        invrms.data_ptr<float>(), dx.data_ptr(),
-                        dw_partial.data_ptr<float>(), dw32.data_ptr<float>(),
-                        dw.data_ptr(), w_bf16, rows, H, P, cur_stream());
-    return {dx, dw};
+    return rms_norm_bwd_impl(dy, nullptr, x, w, invrms);
+}
+
+std::vector<torch::Tensor> add_rms_norm_fwd(torch::Tensor residual, torch::Tensor delta,
+                                            torch::Tensor w, double eps) {
+    return rms_norm_fwd_impl(residual, &delta, w, eps);
+}
+
+std::vector<torch::Tensor> add_rms_norm_bwd(torch::Tensor dy, torch::Tensor dh,
+                                            torch::Tensor h, torch::Tensor w,
+                                            torch::Tensor invrms) {
+    return rms_norm_bwd_impl(dy, &dh, h, w, invrms);
 }
 
 // ---------------------------------------------------------------------------
@@ -64,6 +112,27 @@ std::vector<torch::Tensor> rope_fwd(torch::Tensor q, torch::Tensor k,
     launch_rope(k.data_ptr(), k_out.data_ptr(), cf.data_ptr<float>(), sf.data_ptr<float>(),
                 (long long)B * S * Hk, Hk, D, S, backward, cur_stream());
     return {q_out, k_out};
+}
+
+// Rotates the q and k heads of packed [B, S, (Hq + 2*Hk)*D] rows in place
+// (backward: by -theta, on dqkv) and leaves the v heads alone.
+void rope_packed_(torch::Tensor qkv, torch::Tensor cos_t, torch::Tensor sin_t,
+                  int64_t Hq, int64_t Hk, bool backward) {
+    CHECK_GPU(qkv); CHECK_CONTIG(qkv); CHECK_BF16(qkv);
+    TORCH_CHECK(qkv.dim() == 3, "qkv must be [B, S, (Hq+2*Hk)*D]");
+    TORCH_CHECK(Hq > 0 && Hk > 0 && qkv.size(2) % (Hq + 2 * Hk) == 0,
+                "last dim must be (Hq + 2*Hk) * D");
+    int B = qkv.size(0), S = qkv.size(1);
+    int D = (int)(qkv.size(2) / (Hq + 2 * Hk));
+    TORCH_CHECK(D % 16 == 0 && D <= 1024 && 64 % (D / 16) == 0,
+                "packed rope takes head dims 16, 32, 64, 128, 256, 512, 1024; got ", D);
+    auto cf = cos_t.to(torch::kFloat32).contiguous();
+    auto sf = sin_t.to(torch::kFloat32).contiguous();
+    TORCH_CHECK(cf.dim() == 2 && cf.size(0) == S && cf.size(1) == D &&
+                    sf.sizes() == cf.sizes(),
+                "cos/sin tables must be [S, D]");
+    launch_rope_packed(qkv.data_ptr(), cf.data_ptr<float>(), sf.data_ptr<float>(),
+                       (long long)B * S, (int)Hq, (int)Hk, D, S, backward, cur_stream());
 }
 
 // ---------------------------------------------------------------------------
@@ -311,6 +380,19 @@ std::vector<torch::Tensor> flash_attn_bwd(torch::Tensor dout, torch::Tensor q,
     return flash_attn_bwd_ex(dout, q, k, v, o, lse, causal, /*force_v1=*/false);
 }
 
+// delta[b,h,q] = rowsum(dO * O): the backward's preprocess on its own (every
+// head dim the backward takes), for tests and tools/bench_layer_ops.py.
+torch::Tensor flash_bwd_delta(torch::Tensor dout, torch::Tensor o) {
+    CHECK_GPU(dout); CHECK_CONTIG(dout); CHECK_BF16(dout);
+    CHECK_GPU(o); CHECK_CONTIG(o); CHECK_BF16(o);
+    TORCH_CHECK(dout.dim() == 4 && dout.sizes() == o.sizes(), "dout, o must be [B,S,H,D]");
+    int B = o.size(0), Sq = o.size(1), Hq = o.size(2), D = o.size(3);
+    auto delta = torch::empty({B, Hq, Sq}, o.options().dtype(torch::kFloat32));
+    launch_flash_bwd_delta(dout.data_ptr(), o.data_ptr(), delta.data_ptr<float>(),
+                           B, Sq, Hq, D, cur_stream());
+    return delta;
+}
+
 // The v2 backward with only some of its launches (FLASH_BWD_* mask: 1 delta,
 // 2 dq, 4 dkv), so tools/bench_fa.py can time dq and dkv on their own.
 // Outputs of launches left out are uninitialised.
@@ -337,6 +419,138 @@ std::vector<torch::Tensor> flash_attn_bwd2_parts(torch::Tensor dout, torch::Tens
                                   Hk, D, scale, causal, cur_stream(), (int)parts),
                 "flash_attn_bwd2_parts: no v2 kernel for this shape");
     return {dq, dk_h, dv_h};
+}
+
+// ---------------------------------------------------------------------------
+// Packed attention: q, k, v are read in place from the fused projection's
+// output qkv [B, S, (Hq + 2*Hk)*D] (per token: Hq q heads, Hk k heads, Hk v
+// heads) and the backward writes dq, dk, dv straight into one dqkv of the
+// same layout.  Only the v2 kernels take row strides, so these entry points
+// exist for the shapes v2 takes (D = 128); anything else is an error and
+// the caller keeps the split + contiguous path.
+// ---------------------------------------------------------------------------
+struct PackedDims { int B, S, Hq, Hk, D; int64_t k_off, v_off; };
+
+static PackedDims check_packed(const torch::Tensor& qkv, int64_t Hq, int64_t Hk,
+                               const torch::Tensor* startend) {
+    TORCH_CHECK(qkv.is_cuda(), "qkv must be on GPU");
+    TORCH_CHECK(qkv.scalar_type() == torch::kBFloat16, "qkv must be bf16");
+    TORCH_CHECK(qkv.is_contiguous(), "qkv must be contiguous");
+    TORCH_CHECK(qkv.dim() == 3, "qkv must be [B, S, (Hq+2*Hk)*D]");
+    TORCH_CHECK(Hq > 0 && Hk > 0 && Hq % Hk == 0, "GQA requires Hq % Hk == 0");
+    TORCH_CHECK(qkv.size(2) % (Hq + 2 * Hk) == 0, "last dim must be (Hq + 2*Hk) * D");
+    PackedDims d;
+    d.B = qkv.size(0); d.S = qkv.size(1); d.Hq = (int)Hq; d.Hk = (int)Hk;
+    d.D = (int)(qkv.size(2) / (Hq + 2 * Hk));
+    TORCH_CHECK(d.D == 128, "packed attention needs head dim 128 (the v2 kernels), got ", d.D);
+    TORCH_CHECK(qkv.size(2) < (1LL << 31), "packed row too long");
+    // the dkv kernel's LDS-DMA and every 16-byte load need 16-byte aligned
+    // sources: base pointer, row stride and slice offsets (multiples of
+    // D * 2 = 256 bytes)
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(qkv.data_ptr()) % 16 == 0,
+                "qkv must be 16-byte aligned");
+    d.k_off = Hq * d.D;
+    d.v_off = (Hq + Hk) * d.D;
+    if (startend) {
+        TORCH_CHECK(startend->is_cuda(), "startend must be on GPU");
+        TORCH_CHECK(startend->numel() == (int64_t)d.B * d.S, "startend must be [B, S]");
+    }
+    return d;
+}
+
+static void check_packed_bwd(const PackedDims& d, const torch::Tensor& dout,
+                             const torch::Tensor& o, const torch::Tensor& lse) {
+    auto check_o = [&](const torch::Tensor& t, const char* name) {
+        TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kBFloat16 && t.is_contiguous(),
+                    name, " must be a contiguous bf16 GPU tensor");
+        TORCH_CHECK(t.sizes() == at::IntArrayRef({d.B, d.S, d.Hq, d.D}),
+                    name, " must be [B,S,Hq,D]");
+    };
+    check_o(dout, "dout");
+    check_o(o, "o");
+    TORCH_CHECK(lse.is_cuda() && lse.is_contiguous() &&
+                    lse.scalar_type() == torch::kFloat32 &&
+                    lse.sizes() == at::IntArrayRef({d.B, d.Hq, d.S}),
+                "lse must be a contiguous fp32 [B,Hq,S] GPU tensor");
+}
+
+static std::vector<torch::Tensor> packed_fwd(const torch::Tensor& qkv, int64_t Hq, int64_t Hk,
+                                             bool causal, const torch::Tensor* startend) {
+    PackedDims d = check_packed(qkv, Hq, Hk, startend);
+    auto o = torch::empty({d.B, d.S, d.Hq, d.D}, qkv.options());
+    auto lse = torch::empty({d.B, d.Hq, d.S}, qkv.options().dtype(torch::kFloat32));
+    if (d.B == 0 || d.S == 0) return {o, lse};
+    const auto* base = static_cast<const at::BFloat16*>(qkv.data_ptr());
+    FlashStrides rs = flash_packed_strides(d.Hq, d.Hk, d.D);
+    float scale = 1.0f / std::sqrt((float)d.D);
+    bool ok;
+    if (startend) {
+        auto se = startend->to(torch::kInt32).contiguous();
+        ok = launch_flash_fwd2_mask(base, base + d.k_off, base + d.v_off, o.data_ptr(),
+                                    lse.data_ptr<float>(), se.data_ptr<int>(),
+                                    d.B, d.S, d.S, d.Hq, d.Hk, d.D, scale, cur_stream(), &rs);
+    } else {
+        ok = launch_flash_fwd2(base, base + d.k_off, base + d.v_off, o.data_ptr(),
+                               lse.data_ptr<float>(), d.B, d.S, d.S, d.Hq, d.Hk, d.D,
+                               scale, causal, cur_stream(), &rs);
+    }
+    TORCH_CHECK(ok, "packed attention: no v2 kernel for this shape");
+    return {o, lse};
+}
+
+static torch::Tensor packed_bwd(const torch::Tensor& dout, const torch::Tensor& qkv,
+                                const torch::Tensor& o, const torch::Tensor& lse,
+                                int64_t Hq, int64_t Hk, bool causal,
+                                const torch::Tensor* startend) {
+    PackedDims d = check_packed(qkv, Hq, Hk, startend);
+    check_packed_bwd(d, dout, o, lse);
+    auto dqkv = torch::empty_like(qkv);
+    if (d.B == 0 || d.S == 0) return dqkv;
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(dout.data_ptr()) % 16 == 0,
+                "dout must be 16-byte aligned");
+    auto delta = torch::empty({d.B, d.Hq, d.S}, qkv.options().dtype(torch::kFloat32));
+    const auto* base = static_cast<const at::BFloat16*>(qkv.data_ptr());
+    auto* dbase = static_cast<at::BFloat16*>(dqkv.data_ptr());
+    FlashStrides rs = flash_packed_strides(d.Hq, d.Hk, d.D);
+    float scale = 1.0f / std::sqrt((float)d.D);
+    bool ok;
+    if (startend) {
+        auto se = startend->to(torch::kInt32).contiguous();
+        ok = launch_flash_bwd2_mask(dout.data_ptr(), base, base + d.k_off, base + d.v_off,
+                                    o.data_ptr(), lse.data_ptr<float>(),
+                                    delta.data_ptr<float>(), dbase, dbase + d.k_off,
+                                    dbase + d.v_off, se.data_ptr<int>(),
+                                    d.B, d.S, d.S, d.Hq, d.Hk, d.D, scale, cur_stream(), &rs);
+    } else {
+        ok = launch_flash_bwd2(dout.data_ptr(), base, base + d.k_off, base + d.v_off,
+                               o.data_ptr(), lse.data_ptr<float>(), delta.data_ptr<float>(),
+                               dbase, dbase + d.k_off, dbase + d.v_off,
+                               d.B, d.S, d.S, d.Hq, d.Hk, d.D, scale, causal, cur_stream(),
+                               FLASH_BWD_ALL, &rs);
+    }
+    TORCH_CHECK(ok, "packed attention: no v2 kernel for this shape");
+    return dqkv;
+}
+
+std::vector<torch::Tensor> flash_attn_packed_fwd(torch::Tensor qkv, int64_t Hq, int64_t Hk,
+                                                 bool causal) {
+    return packed_fwd(qkv, Hq, Hk, causal, nullptr);
+}
+
+torch::Tensor flash_attn_packed_bwd(torch::Tensor dout, torch::Tensor qkv, torch::Tensor o,
+                                    torch::Tensor lse, int64_t Hq, int64_t Hk, bool causal) {
+    return packed_bwd(dout, qkv, o, lse, Hq, Hk, causal, nullptr);
+}
+
+std::vector<torch::Tensor> flashmask_attn_packed_fwd(torch::Tensor qkv, int64_t Hq, int64_t Hk,
+                                                     torch::Tensor startend) {
+    return packed_fwd(qkv, Hq, Hk, true, &startend);
+}
+
+torch::Tensor flashmask_attn_packed_bwd(torch::Tensor dout, torch::Tensor qkv, torch::Tensor o,
+                                        torch::Tensor lse, int64_t Hq, int64_t Hk,
+                                        torch::Tensor startend) {
+    return packed_bwd(dout, qkv, o, lse, Hq, Hk, true, &startend);
 }
 
 // ---------------------------------------------------------------------------
@@ -589,7 +803,14 @@ torch::Tensor wint8_gemv(torch::Tensor x, torch::Tensor wq, torch::Tensor scale)
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("rms_norm_fwd", &rms_norm_fwd);
     m.def("rms_norm_bwd", &rms_norm_bwd);
+    m.def("add_rms_norm_fwd", &add_rms_norm_fwd);
+    m.def("add_rms_norm_bwd", &add_rms_norm_bwd);
     m.def("rope_fwd", &rope_fwd);
+    m.def("rope_packed_", &rope_packed_);
+    m.def("flash_attn_packed_fwd", &flash_attn_packed_fwd);
+    m.def("flash_attn_packed_bwd", &flash_attn_packed_bwd);
+    m.def("flashmask_attn_packed_fwd", &flashmask_attn_packed_fwd);
+    m.def("flashmask_attn_packed_bwd", &flashmask_attn_packed_bwd);
     m.def("swiglu_fwd", &swiglu_fwd);
     m.def("swiglu_bwd", &swiglu_bwd);
     m.def("cross_entropy_fwd", &cross_entropy_fwd);
@@ -599,6 +820,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("permlane_probe", &permlane_probe);
     m.def("lds_image_probe", &lds_image_probe);
     m.def("flash_attn_bwd2_parts", &flash_attn_bwd2_parts);
+    m.def("flash_bwd_delta", &flash_bwd_delta);
     m.def("apply_repetition_penalty", &apply_repetition_penalty);
     m.def("topp_sample", &topp_sample,
           py::arg("logits"), py::arg("temperature"), py::arg("top_p"),

@@ -270,29 +270,60 @@ __global__ __launch_bounds__(FA_BLOCK) void flash_fwd_kernel(
 // ---------------------------------------------------------------------------
 // backward preprocess: delta[b,h,q] = rowsum(dO * O).  Shared with the v2
 // backward (flash_attn_bwd_v2.hip) through launch_flash_bwd_delta.
+//
+// A block takes DELTA_QT consecutive q positions of one batch entry with all
+// their heads: DELTA_QT*Hq rows that are contiguous in dO and O.  D/8 lanes
+// share a row (one 16-byte load of each tensor per lane, 64/(D/8) rows per
+// wave) and the row sums go through LDS, which turns the [q][h] order they
+// are produced in into the [h][q] order of delta: every head's DELTA_QT
+// floats are written as one contiguous segment.
 // ---------------------------------------------------------------------------
+#define DELTA_BLOCK 256
+#define DELTA_QT 32
 template <int D>
-__global__ void flash_bwd_delta_kernel(
+__global__ __launch_bounds__(DELTA_BLOCK) void flash_bwd_delta_kernel(
     const ushort_t* __restrict__ dout, const ushort_t* __restrict__ o,
     float* __restrict__ delta, int B, int Sq, int Hq) {
-    long long row = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    long long total = (long long)B * Sq * Hq;
-    if (row >= total) return;
-    int lane = threadIdx.x & 63;
-    const ushort_t* dor = dout + row * D;
-    const ushort_t* orow = o + row * D;
-    float acc = 0.f;
+    constexpr int LPR = D / 8;                  // lanes per row
+    constexpr int RPI = DELTA_BLOCK / LPR;      // rows per block iteration
+    extern __shared__ float delta_lds[];        // [Hq][DELTA_QT + 1]
+    const int ntq = (Sq + DELTA_QT - 1) / DELTA_QT;
+    const int b = blockIdx.x / ntq;
+    const int q0 = (blockIdx.x % ntq) * DELTA_QT;
+    const int nq = min(DELTA_QT, Sq - q0);
+    const int nrows = nq * Hq;
+    const long long base = ((long long)b * Sq + q0) * Hq * D + (threadIdx.x % LPR) * 8;
+    const ushort_t* dop = dout + base;
+    const ushort_t* op = o + base;
+#pragma unroll 4
+    for (int r = threadIdx.x / LPR; r < nrows; r += RPI) {
+        short8v dv = *reinterpret_cast<const short8v*>(dop + (long long)r * D);
+        short8v ov = *reinterpret_cast<const short8v*>(op + (long long)r * D);
+        // Summation tree of the one-row-per-wave kernel this replaces (lane l
+        // summed elements 2l and 2l+1, then a 64-lane xor butterfly from
+        // offset 32 down to 1), so delta, and dq/dk/dv after it, keep their
+        // bits: pair sums pr[m] stand for that kernel's lanes 4*j + m (j =
+        // this lane within the row); butterfly over j first, then over m.
+        float pr[4];
 #pragma unroll
-    for (int i = lane * 2; i < D; i += 128) {
-        acc += bf16_to_f32(dor[i]) * bf16_to_f32(orow[i]);
-        acc += bf16_to_f32(dor[i + 1]) * bf16_to_f32(orow[i + 1]);
+        for (int m = 0; m < 4; m++) {
+            pr[m] = 0.f;
+            pr[m] += bf16_to_f32((ushort_t)dv[2 * m]) * bf16_to_f32((ushort_t)ov[2 * m]);
+            pr[m] += bf16_to_f32((ushort_t)dv[2 * m + 1]) * bf16_to_f32((ushort_t)ov[2 * m + 1]);
+        }
+#pragma unroll
+        for (int off = LPR / 2; off > 0; off >>= 1)
+#pragma unroll
+            for (int m = 0; m < 4; m++) pr[m] += __shfl_xor(pr[m], off, 64);
+        float acc = (pr[0] + pr[2]) + (pr[1] + pr[3]);
+        if (threadIdx.x % LPR == 0)
+            delta_lds[(r % Hq) * (DELTA_QT + 1) + r / Hq] = acc;   // r = qi*Hq + h
     }
-    acc = wave_reduce_sum(acc);
-    if (lane == 0) {
-        long long h = row % Hq;
-        long long bq = row / Hq;
-        long long bb = bq / Sq, qi = bq % Sq;
-        delta[(bb * Hq + h) * Sq + qi] = acc;
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < Hq * DELTA_QT; idx += DELTA_BLOCK) {
+        int h = idx / DELTA_QT, qi = idx % DELTA_QT;
+        if (qi < nq)
+            delta[((long long)b * Hq + h) * Sq + q0 + qi] = delta_lds[h * (DELTA_QT + 1) + qi];
     }
 }
 // ---------------------------------------------------------------------------
@@ -765,10 +796,13 @@ void launch_flash_fwd_mask(const void* q, const void* k, const void* v, void* o,
 template <int D>
 static void flash_bwd_delta_t(const void* dout, const void* o, float* delta,
                               int B, int Sq, int Hq, hipStream_t stream) {
-    constexpr int BLOCK = 512;   // one row per wave, 8 rows per block
-    long long rows = (long long)B * Sq * Hq;
-    int grid = (int)((rows + BLOCK / 64 - 1) / (BLOCK / 64));
-    hipLaunchKernelGGL(flash_bwd_delta_kernel<D>, dim3(grid), dim3(BLOCK), 0, stream,
+    if (B <= 0 || Sq <= 0) return;
+    size_t lds = (size_t)Hq * (DELTA_QT + 1) * sizeof(float);
+    if (lds > 64 * 1024)
+        throw std::runtime_error("flash attention backward: delta kernel takes at most " +
+                                 std::to_string(64 * 1024 / ((DELTA_QT + 1) * 4)) + " heads");
+    int grid = B * ((Sq + DELTA_QT - 1) / DELTA_QT);
+    hipLaunchKernelGGL(flash_bwd_delta_kernel<D>, dim3(grid), dim3(DELTA_BLOCK), lds, stream,
                        (const ushort_t*)dout, (const ushort_t*)o, delta, B, Sq, Hq);
 }
 

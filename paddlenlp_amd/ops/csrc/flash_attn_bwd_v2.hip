@@ -38,6 +38,7 @@ __global__ __launch_bounds__(FB2_BLOCK) void flash_bwd2_dq_kernel(
     const ushort_t* __restrict__ v, const ushort_t* __restrict__ dout,
     const float* __restrict__ lse, const float* __restrict__ delta,
     ushort_t* __restrict__ dq, const int* __restrict__ startend,
+    FlashStrides rs,   // row strides (elements) of q, k/v, dq; dout is contiguous
     int B, int Sq, int Skv, int Hq, int Hk, float scale, int causal) {
     constexpr int BLKN = 64;
     constexpr int DSTEPS = D / 16;
@@ -67,12 +68,15 @@ __global__ __launch_bounds__(FB2_BLOCK) void flash_bwd2_dq_kernel(
     const int qg = qw + l32;
     const int causal_off = Skv - Sq;
 
-    const long long q_row_stride = (long long)Hq * D;
-    const long long kv_row_stride = (long long)Hk * D;
-    const ushort_t* q_ptr = q + ((long long)b * Sq * Hq + hq) * D;
+    // q, k, v, dq point at head 0 of token 0 and may be slices of a packed
+    // [B, S, (Hq + 2*Hk)*D] tensor (see flash_attn_v2.hip)
+    const long long q_row_stride = rs.q;
+    const long long kv_row_stride = rs.kv;
+    const long long do_row_stride = (long long)Hq * D;
+    const ushort_t* q_ptr = q + (long long)b * Sq * q_row_stride + (long long)hq * D;
     const ushort_t* do_ptr = dout + ((long long)b * Sq * Hq + hq) * D;
-    const ushort_t* k_ptr = k + ((long long)b * Skv * Hk + hk) * D;
-    const ushort_t* v_ptr = v + ((long long)b * Skv * Hk + hk) * D;
+    const ushort_t* k_ptr = k + (long long)b * Skv * kv_row_stride + (long long)hk * D;
+    const ushort_t* v_ptr = v + (long long)b * Skv * kv_row_stride + (long long)hk * D;
 
     // stationary per-lane: Q^T and dO^T B-fragments (one q row each)
     frag8 aq[DSTEPS], ado[DSTEPS];
@@ -83,7 +87,7 @@ __global__ __launch_bounds__(FB2_BLOCK) void flash_bwd2_dq_kernel(
             aq[kk] = *reinterpret_cast<const frag8*>(
                 q_ptr + (long long)qg * q_row_stride + kk * 16 + hi * 8);
             ado[kk] = *reinterpret_cast<const frag8*>(
-                do_ptr + (long long)qg * q_row_stride + kk * 16 + hi * 8);
+                do_ptr + (long long)qg * do_row_stride + kk * 16 + hi * 8);
         }
         lse_q = lse[((long long)b * Hq + hq) * Sq + qg];
         dl_q = delta[((long long)b * Hq + hq) * Sq + qg];
@@ -236,7 +240,7 @@ __global__ __launch_bounds__(FB2_BLOCK) void flash_bwd2_dq_kernel(
     for (int r = 0; r < 16; r++) {
         int qrow = qw + crow32(r, hi);
         if (qrow >= Sq) continue;
-        ushort_t* dqr = dq + ((long long)b * Sq + qrow) * q_row_stride + (long long)hq * D;
+        ushort_t* dqr = dq + ((long long)b * Sq + qrow) * rs.dq + (long long)hq * D;
 #pragma unroll
         for (int n = 0; n < NDT; n++)
             dqr[n * 32 + l32] = f32_to_bf16(acc_dq[n][r]);
@@ -263,6 +267,7 @@ __global__ __launch_bounds__(FB2_BLOCK, 1) void flash_bwd2_dkv_kernel(
     const float* __restrict__ lse, const float* __restrict__ delta,
     ushort_t* __restrict__ dk, ushort_t* __restrict__ dv,
     const int* __restrict__ startend,
+    FlashStrides rs,   // row strides (elements) of q, k/v, dk/dv; dout is contiguous
     int B, int Sq, int Skv, int Hq, int Hk, float scale, int causal) {
     static_assert(D == 128, "the dual-use image is laid out for 128-column tiles");
     constexpr int BLKQ = 64;               // q tile
@@ -308,10 +313,9 @@ __global__ __launch_bounds__(FB2_BLOCK, 1) void flash_bwd2_dkv_kernel(
         if (lane == 0) blk_max_lds[wave] = wave_max_end;
     }
 
-    const long long q_row_stride = (long long)Hq * D;
-    const long long kv_row_stride = (long long)Hk * D;
-    const ushort_t* k_ptr = k + ((long long)b * Skv * Hk + hk) * D;
-    const ushort_t* v_ptr = v + ((long long)b * Skv * Hk + hk) * D;
+    const long long do_row_stride = (long long)Hq * D;
+    const ushort_t* k_ptr = k + (long long)b * Skv * rs.kv + (long long)hk * D;
+    const ushort_t* v_ptr = v + (long long)b * Skv * rs.kv + (long long)hk * D;
 
     // stationary per-lane: K^T and V^T B-fragments (one kv row each).
     // Ordinary global loads: they retire before the first DMA is issued.
@@ -320,9 +324,9 @@ __global__ __launch_bounds__(FB2_BLOCK, 1) void flash_bwd2_dkv_kernel(
 #pragma unroll
         for (int kk = 0; kk < DSTEPS; kk++) {
             bk[kk] = *reinterpret_cast<const frag8*>(
-                k_ptr + (long long)kvg_lane * kv_row_stride + kk * 16 + hi * 8);
+                k_ptr + (long long)kvg_lane * rs.kv + kk * 16 + hi * 8);
             bv[kk] = *reinterpret_cast<const frag8*>(
-                v_ptr + (long long)kvg_lane * kv_row_stride + kk * 16 + hi * 8);
+                v_ptr + (long long)kvg_lane * rs.kv + kk * 16 + hi * 8);
         }
     } else {
 #pragma unroll
@@ -359,7 +363,10 @@ __global__ __launch_bounds__(FB2_BLOCK, 1) void flash_bwd2_dkv_kernel(
     // their P and dS.
     auto issue_tile = [&](int g, int qt, int buf) {
         const int hq = hk * G + g;
-        const long long head_off = ((long long)b * Sq * Hq + hq) * D;
+        // the DMA source must be 16-byte aligned: the launcher checks the q
+        // base and row stride, a head starts at a multiple of 256 bytes
+        const long long do_off = ((long long)b * Sq * Hq + hq) * D;
+        const long long q_off = (long long)b * Sq * rs.q + (long long)hq * D;
         const int q_tb = qt * BLKQ;
         // the kernel sits at the register cap: recompute the per-lane source
         // offsets every tile (a few VALU ops) rather than let the compiler
@@ -370,10 +377,11 @@ __global__ __launch_bounds__(FB2_BLOCK, 1) void flash_bwd2_dkv_kernel(
         for (int i = 0; i < 2; i++) {
             const int piece = wave * 2 + i;
             const int src_row = min(q_tb + img_fill_row(piece, ln), Sq - 1);
-            const long long src = head_off + (long long)src_row * q_row_stride +
-                                  img_fill_chunk(piece, ln) * 8;
-            lds_dma16(q + src, &qd_lds[buf][0][piece * 512]);
-            lds_dma16(dout + src, &qd_lds[buf][1][piece * 512]);
+            const int chunk = img_fill_chunk(piece, ln) * 8;
+            lds_dma16(q + (q_off + (long long)src_row * rs.q + chunk),
+                      &qd_lds[buf][0][piece * 512]);
+            lds_dma16(dout + (do_off + (long long)src_row * do_row_stride + chunk),
+                      &qd_lds[buf][1][piece * 512]);
         }
         if (wave < 2) {
             const float* row = (wave == 0 ? lse : delta) +
@@ -474,12 +482,11 @@ __global__ __launch_bounds__(FB2_BLOCK, 1) void flash_bwd2_dkv_kernel(
     }
 
     // epilogue: acc C-layout [kv][d] (col = d, row = kv within the wave)
-    const long long out_row_stride = (long long)Hk * D;
 #pragma unroll
     for (int r = 0; r < 16; r++) {
         int kvr = kvw + crow32(r, hi);
         if (kvr >= Skv) continue;
-        long long base = ((long long)b * Skv + kvr) * out_row_stride + (long long)hk * D;
+        long long base = ((long long)b * Skv + kvr) * rs.dkv + (long long)hk * D;
 #pragma unroll
         for (int n = 0; n < NDT; n++) {
             dk[base + n * 32 + l32] = f32_to_bf16(acc_dk[n][r]);
@@ -531,8 +538,10 @@ bool launch_flash_bwd2(const void* dout, const void* q, const void* k, const voi
                        const void* o, const float* lse, float* delta,
                        void* dq, void* dk, void* dv,
                        int B, int Sq, int Skv, int Hq, int Hk, int D,
-                       float scale, bool causal, hipStream_t stream, int parts) {
+                       float scale, bool causal, hipStream_t stream, int parts,
+                       const FlashStrides* strides) {
     if (D != 128 || (Hq % Hk) != 0) return false;
+    const FlashStrides rs = strides ? *strides : flash_contiguous_strides(Hq, Hk, D);
     if (parts & FLASH_BWD_DELTA)
         launch_flash_bwd_delta(dout, o, delta, B, Sq, Hq, D, stream);
     if (parts & FLASH_BWD_DQ) {
@@ -540,7 +549,7 @@ bool launch_flash_bwd2(const void* dout, const void* q, const void* k, const voi
         hipLaunchKernelGGL((flash_bwd2_dq_kernel<128, false>), gq, dim3(FB2_BLOCK), 0, stream,
                            (const ushort_t*)q, (const ushort_t*)k, (const ushort_t*)v,
                            (const ushort_t*)dout, lse, delta, (ushort_t*)dq,
-                           (const int*)nullptr,
+                           (const int*)nullptr, rs,
                            B, Sq, Skv, Hq, Hk, scale, causal ? 1 : 0);
     }
     if (parts & FLASH_BWD_DKV) {
@@ -548,7 +557,7 @@ bool launch_flash_bwd2(const void* dout, const void* q, const void* k, const voi
         hipLaunchKernelGGL((flash_bwd2_dkv_kernel<128, false>), gkv, dim3(FB2_BLOCK), 0, stream,
                            (const ushort_t*)q, (const ushort_t*)k, (const ushort_t*)v,
                            (const ushort_t*)dout, lse, delta, (ushort_t*)dk, (ushort_t*)dv,
-                           (const int*)nullptr,
+                           (const int*)nullptr, rs,
                            B, Sq, Skv, Hq, Hk, scale, causal ? 1 : 0);
     }
     return true;
@@ -559,18 +568,20 @@ bool launch_flash_bwd2_mask(const void* dout, const void* q, const void* k,
                             float* delta, void* dq, void* dk, void* dv,
                             const int* startend,
                             int B, int Sq, int Skv, int Hq, int Hk, int D,
-                            float scale, hipStream_t stream) {
+                            float scale, hipStream_t stream,
+                            const FlashStrides* strides) {
     if (D != 128 || (Hq % Hk) != 0) return false;
+    const FlashStrides rs = strides ? *strides : flash_contiguous_strides(Hq, Hk, D);
     launch_flash_bwd_delta(dout, o, delta, B, Sq, Hq, D, stream);
     dim3 gq((Sq + 255) / 256, B * Hq);
     hipLaunchKernelGGL((flash_bwd2_dq_kernel<128, true>), gq, dim3(FB2_BLOCK), 0, stream,
                        (const ushort_t*)q, (const ushort_t*)k, (const ushort_t*)v,
-                       (const ushort_t*)dout, lse, delta, (ushort_t*)dq, startend,
+                       (const ushort_t*)dout, lse, delta, (ushort_t*)dq, startend, rs,
                        B, Sq, Skv, Hq, Hk, scale, 1);
     dim3 gkv((Skv + 255) / 256, B * Hk);
     hipLaunchKernelGGL((flash_bwd2_dkv_kernel<128, true>), gkv, dim3(FB2_BLOCK), 0, stream,
                        (const ushort_t*)q, (const ushort_t*)k, (const ushort_t*)v,
                        (const ushort_t*)dout, lse, delta, (ushort_t*)dk, (ushort_t*)dv,
-                       startend, B, Sq, Skv, Hq, Hk, scale, 1);
+                       startend, rs, B, Sq, Skv, Hq, Hk, scale, 1);
     return true;
 }

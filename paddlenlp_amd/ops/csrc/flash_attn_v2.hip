@@ -79,6 +79,7 @@ __global__ __launch_bounds__(FA2_BLOCK) void flash_fwd2_kernel(
     ushort_t* __restrict__ o,         // [B, Sq, Hq, D]
     float* __restrict__ lse,          // [B, Hq, Sq]
     const int* __restrict__ startend, // FlashMask [B, Skv] (MASKED only)
+    FlashStrides rs,                  // row strides of q and k/v (elements)
     int B, int Sq, int Skv, int Hq, int Hk, float scale, int causal) {
     constexpr int DSTEPS = D / 16;    // K-steps of the S^T MFMAs
     constexpr int NDT = D / 32;       // 32-col d-tiles of O
@@ -121,11 +122,15 @@ __global__ __launch_bounds__(FA2_BLOCK) void flash_fwd2_kernel(
     const int qg = qw + l32;                 // this lane's q row (softmax owner)
     const int causal_off = Skv - Sq;
 
-    const long long q_row_stride = (long long)Hq * D;
-    const long long kv_row_stride = (long long)Hk * D;
-    const ushort_t* q_ptr = q + ((long long)b * Sq * Hq + hq) * D;
-    const ushort_t* k_ptr = k + ((long long)b * Skv * Hk + hk) * D;
-    const ushort_t* v_ptr = v + ((long long)b * Skv * Hk + hk) * D;
+    // q, k, v point at head 0 of token 0 and may be slices of one packed
+    // [B, S, (Hq + 2*Hk)*D] tensor: a token row is rs.* elements apart and
+    // a batch entry S rows.  o is contiguous.
+    const long long q_row_stride = rs.q;
+    const long long kv_row_stride = rs.kv;
+    const long long o_row_stride = (long long)Hq * D;
+    const ushort_t* q_ptr = q + (long long)b * Sq * q_row_stride + (long long)hq * D;
+    const ushort_t* k_ptr = k + (long long)b * Skv * kv_row_stride + (long long)hk * D;
+    const ushort_t* v_ptr = v + (long long)b * Skv * kv_row_stride + (long long)hk * D;
 
     // Q B-fragments in registers: lane l holds Q[qw + l32][kk*16 + hi*8 + j]
     frag8 aq[DSTEPS];
@@ -368,7 +373,7 @@ __global__ __launch_bounds__(FA2_BLOCK) void flash_fwd2_kernel(
         int qrow = qw + crow32(r, hi);
         if (qrow >= Sq) continue;
         float il = __shfl(inv_l, crow32(r, hi), 64);
-        ushort_t* orow = o + ((long long)b * Sq + qrow) * q_row_stride + (long long)hq * D;
+        ushort_t* orow = o + ((long long)b * Sq + qrow) * o_row_stride + (long long)hq * D;
 #pragma unroll
         for (int n = 0; n < NDT; n++)
             orow[n * 32 + l32] = f32_to_bf16(acc_o[n][r] * il);
@@ -393,12 +398,14 @@ void launch_permlane_probe(int* out0, int* out1, hipStream_t stream) {
 
 bool launch_flash_fwd2(const void* q, const void* k, const void* v, void* o,
                        float* lse, int B, int Sq, int Skv, int Hq, int Hk,
-                       int D, float scale, bool causal, hipStream_t stream) {
+                       int D, float scale, bool causal, hipStream_t stream,
+                       const FlashStrides* strides) {
     if (D != 128 || (Hq % Hk) != 0) return false;
+    const FlashStrides rs = strides ? *strides : flash_contiguous_strides(Hq, Hk, D);
     dim3 grid((Sq + FA2_BLKM - 1) / FA2_BLKM, B * Hq);
     hipLaunchKernelGGL((flash_fwd2_kernel<128, false>), grid, dim3(FA2_BLOCK), 0, stream,
                        (const ushort_t*)q, (const ushort_t*)k, (const ushort_t*)v,
-                       (ushort_t*)o, lse, (const int*)nullptr,
+                       (ushort_t*)o, lse, (const int*)nullptr, rs,
                        B, Sq, Skv, Hq, Hk, scale, causal ? 1 : 0);
     return true;
 }
@@ -406,12 +413,14 @@ bool launch_flash_fwd2(const void* q, const void* k, const void* v, void* o,
 bool launch_flash_fwd2_mask(const void* q, const void* k, const void* v,
                             void* o, float* lse, const int* startend,
                             int B, int Sq, int Skv, int Hq, int Hk,
-                            int D, float scale, hipStream_t stream) {
+                            int D, float scale, hipStream_t stream,
+                            const FlashStrides* strides) {
     if (D != 128 || (Hq % Hk) != 0) return false;
+    const FlashStrides rs = strides ? *strides : flash_contiguous_strides(Hq, Hk, D);
     dim3 grid((Sq + FA2_BLKM - 1) / FA2_BLKM, B * Hq);
     hipLaunchKernelGGL((flash_fwd2_kernel<128, true>), grid, dim3(FA2_BLOCK), 0,
                        stream, (const ushort_t*)q, (const ushort_t*)k,
-                       (const ushort_t*)v, (ushort_t*)o, lse, startend,
+                       (const ushort_t*)v, (ushort_t*)o, lse, startend, rs,
                        B, Sq, Skv, Hq, Hk, scale, 1);
     return true;
 }

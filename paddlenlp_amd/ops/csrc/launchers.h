@@ -15,15 +15,29 @@
 }
 
 // ---- rms_norm.hip / rope.hip / swiglu.hip / cross_entropy.hip ----
-void launch_rms_norm_fwd(const void* x, const void* w, void* y, float* invrms,
+// delta != nullptr fuses the residual add: h = bf16(x + delta), y = norm(h).
+// Without it h is unused and y = norm(x).
+void launch_rms_norm_fwd(const void* x, const void* delta, const void* w, void* h,
+                         void* y, float* invrms,
                          long long rows, int H, float eps, hipStream_t stream);
-void launch_rms_norm_bwd(const void* dy, const void* x, const void* w,
+// Number of fp32 partial dw rows [P, H] the backward needs for this shape,
+// and whether they must be zero-filled (only the streaming path for
+// H > 8192 accumulates into them; the register path overwrites them).
+int rms_norm_bwd_partials(long long rows, int H, bool* needs_zero);
+// dh != nullptr adds the residual-stream gradient: dx = bf16(bf16(dx_norm) + dh).
+// dw32 must be zero-filled.
+void launch_rms_norm_bwd(const void* dy, const void* x, const void* dh, const void* w,
                          const float* invrms, void* dx, float* dw_partial,
                          float* dw32, void* dw, bool dw_is_bf16,
                          long long rows, int H, int P, hipStream_t stream);
 void launch_rope(const void* x, void* out, const float* cos_t, const float* sin_t,
                  long long n_rows, int H, int D, int S, bool backward,
                  hipStream_t stream);
+// In-place rotation of the first Hq + Hk heads of each packed
+// [(Hq + 2*Hk) * D] row; the V heads are not touched.  D % 16 == 0.
+void launch_rope_packed(void* qkv, const float* cos_t, const float* sin_t,
+                        long long n_tokens, int Hq, int Hk, int D, int S,
+                        bool backward, hipStream_t stream);
 void launch_swiglu_fwd(const void* x, void* y, long long N, int I, hipStream_t stream);
 void launch_swiglu_bwd(const void* dy, const void* x, void* dx, long long N, int I,
                        hipStream_t stream);
@@ -75,6 +89,22 @@ void launch_flash_bwd_delta(const void* dout, const void* o, float* delta,
 
 // ---- flash_attn_v2.hip / flash_attn_bwd_v2.hip: 8-wave 32x32 kernels.
 // Return false (nothing launched) when the shape is not theirs. ----
+//
+// Row strides, in elements, of the tensors the v2 kernels may read or write
+// in place inside a packed [B, S, (Hq + 2*Hk)*D] qkv / dqkv tensor.  Each
+// pointer addresses head 0 of token 0 of its tensor; token rows are one
+// stride apart and a batch entry is S rows.  o, dout, lse and delta are
+// always contiguous.  k and v have one shape and come from one place, so
+// they share a stride (kv), as do dk and dv (dkv): the kernels compute one
+// row offset for the pair.  nullptr strides = contiguous [B,S,H,D] tensors.
+struct FlashStrides { int q, kv, dq, dkv; };
+inline FlashStrides flash_contiguous_strides(int Hq, int Hk, int D) {
+    return {Hq * D, Hk * D, Hq * D, Hk * D};
+}
+inline FlashStrides flash_packed_strides(int Hq, int Hk, int D) {
+    int w = (Hq + 2 * Hk) * D;
+    return {w, w, w, w};
+}
 void launch_mfma32_probe(const void* A, const void* B, float* C, hipStream_t stream);
 void launch_permlane_probe(int* out0, int* out1, hipStream_t stream);
 // X, out_row, out_tr: 64 x 128 bf16 (see mfma.h dual-use image)
@@ -82,11 +112,13 @@ void launch_lds_image_probe(const void* X, void* out_row, void* out_tr,
                             hipStream_t stream);
 bool launch_flash_fwd2(const void* q, const void* k, const void* v, void* o,
                        float* lse, int B, int Sq, int Skv, int Hq, int Hk,
-                       int D, float scale, bool causal, hipStream_t stream);
+                       int D, float scale, bool causal, hipStream_t stream,
+                       const FlashStrides* strides = nullptr);
 bool launch_flash_fwd2_mask(const void* q, const void* k, const void* v,
                             void* o, float* lse, const int* startend,
                             int B, int Sq, int Skv, int Hq, int Hk,
-                            int D, float scale, hipStream_t stream);
+                            int D, float scale, hipStream_t stream,
+                            const FlashStrides* strides = nullptr);
 // parts: which of the three backward launches to issue (tools/bench_fa.py
 // times dq and dkv on their own; everything else takes all three)
 enum { FLASH_BWD_DELTA = 1, FLASH_BWD_DQ = 2, FLASH_BWD_DKV = 4, FLASH_BWD_ALL = 7 };
@@ -95,13 +127,15 @@ bool launch_flash_bwd2(const void* dout, const void* q, const void* k, const voi
                        void* dq, void* dk, void* dv,
                        int B, int Sq, int Skv, int Hq, int Hk, int D,
                        float scale, bool causal, hipStream_t stream,
-                       int parts = FLASH_BWD_ALL);
+                       int parts = FLASH_BWD_ALL,
+                       const FlashStrides* strides = nullptr);
 bool launch_flash_bwd2_mask(const void* dout, const void* q, const void* k,
                             const void* v, const void* o, const float* lse,
                             float* delta, void* dq, void* dk, void* dv,
                             const int* startend,
                             int B, int Sq, int Skv, int Hq, int Hk, int D,
-                            float scale, hipStream_t stream);
+                            float scale, hipStream_t stream,
+                            const FlashStrides* strides = nullptr);
 
 // ---- paged_attn.hip / paged_attn_v2.hip ----
 int paged_decode_nsplit(int B, int Hk);

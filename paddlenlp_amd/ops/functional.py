@@ -75,6 +75,50 @@ def rms_norm(x: torch.Tensor, weight: torch.Tensor, eps: float = 1e-6) -> torch.
     return reference.rms_norm(x, weight, eps)
 
 
+def layer_fusion_enabled() -> bool:
+    """PNLP_LAYER_FUSION=0 selects the unfused layer composition (separate
+    residual adds, split + contiguous q/k/v, out-of-place rope) for A/B runs.
+    Default: the fused add+norm and the packed rope/attention path."""
+    return os.environ.get("PNLP_LAYER_FUSION", "1") != "0"
+
+
+class _AddRMSNormFunction(torch.autograd.Function):
+    """h = residual + delta; y = rms_norm(h).  One kernel each way; both are
+    bit-equal to the separate add and rms_norm."""
+
+    @staticmethod
+    def forward(ctx, residual, delta, weight, eps):
+        C = _load_extension()
+        h, y, invrms = C.add_rms_norm_fwd(residual.contiguous(), delta.contiguous(), weight, eps)
+        ctx.save_for_backward(h, weight, invrms)
+        ctx.set_materialize_grads(False)
+        return h, y
+
+    @staticmethod
+    def backward(ctx, dh, dy):
+        C = _load_extension()
+        h, weight, invrms = ctx.saved_tensors
+        if dy is None:
+            return dh, dh, None, None
+        if dh is None:  # h has no other consumer (the final norm)
+            dx, dw = C.rms_norm_bwd(dy.contiguous(), h, weight, invrms)
+        else:
+            dx, dw = C.add_rms_norm_bwd(dy.contiguous(), dh.contiguous(), h, weight, invrms)
+        return dx, dx, dw, None
+
+
+def add_rms_norm(residual: torch.Tensor, delta: torch.Tensor, weight: torch.Tensor,
+                 eps: float = 1e-6):
+    """Returns (h, y) with h = residual + delta and y = rms_norm(h)."""
+    if (residual.is_cuda and residual.dtype == torch.bfloat16
+            and delta.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16
+            and residual.shape == delta.shape and residual.shape[-1] % 8 == 0
+            and os.environ.get("PNLP_DETERMINISTIC", "0") != "1"):
+        return _AddRMSNormFunction.apply(residual, delta, weight, eps)
+    h = residual + delta
+    return h, rms_norm(h, weight, eps)
+
+
 # ---------------------------------------------------------------------------
 # Rotary position embedding (fused, Llama rotate-half convention)
 # ---------------------------------------------------------------------------
@@ -197,6 +241,82 @@ def flash_attention(
         q, k, v, causal=causal, attn_mask=attn_mask,
         startend_row_indices=startend_row_indices,
     )
+
+
+class _PackedRopeAttnFunction(torch.autograd.Function):
+    """Rope + causal attention on the fused QKV projection's output
+    [B, S, (Hq + 2*Hk)*D], with no layout copies: rope rotates the q and k
+    heads in place, the v2 attention kernels read q/k/v through row strides,
+    and the backward writes dq/dk/dv into one packed dqkv that the rope
+    backward then rotates in place."""
+
+    @staticmethod
+    def forward(ctx, qkv, cos, sin, Hq, Hk, startend):
+        C = _load_extension()
+        C.rope_packed_(qkv, cos, sin, Hq, Hk, False)
+        ctx.mark_dirty(qkv)
+        if startend is None:
+            o, lse = C.flash_attn_packed_fwd(qkv, Hq, Hk, True)
+        else:
+            o, lse = C.flashmask_attn_packed_fwd(qkv, Hq, Hk, startend)
+        ctx.save_for_backward(qkv, o, lse, cos, sin, startend)
+        ctx.heads = (Hq, Hk)
+        ctx.set_materialize_grads(False)
+        return qkv, o
+
+    @staticmethod
+    def backward(ctx, dqkv_rot, do):
+        C = _load_extension()
+        qkv, o, lse, cos, sin, startend = ctx.saved_tensors
+        Hq, Hk = ctx.heads
+        if do is None:
+            dqkv = torch.zeros_like(qkv) if dqkv_rot is None else dqkv_rot.clone()
+        else:
+            if startend is None:
+                dqkv = C.flash_attn_packed_bwd(do.contiguous(), qkv, o, lse, Hq, Hk, True)
+            else:
+                dqkv = C.flashmask_attn_packed_bwd(do.contiguous(), qkv, o, lse, Hq, Hk,
+                                                   startend)
+            if dqkv_rot is not None:  # the rotated qkv has another consumer
+                dqkv += dqkv_rot
+        C.rope_packed_(dqkv, cos, sin, Hq, Hk, True)
+        return dqkv, None, None, None, None, None
+
+
+def packed_rope_attention_supported(qkv: torch.Tensor, num_heads: int, num_kv_heads: int,
+                                    startend_row_indices=None) -> bool:
+    """True where the packed path has kernels: a contiguous bf16 GPU tensor
+    that owns its memory, head dim 128 (the v2 attention kernels)."""
+    if not (qkv.is_cuda and qkv.dtype == torch.bfloat16 and qkv.dim() == 3):
+        return False
+    # rope runs in place: not on a view of other data, not on a parameter
+    if not qkv.is_contiguous() or qkv._is_view() or (qkv.is_leaf and qkv.requires_grad):
+        return False
+    if num_kv_heads <= 0 or num_heads % num_kv_heads:
+        return False
+    if qkv.shape[-1] != (num_heads + 2 * num_kv_heads) * 128:
+        return False
+    if startend_row_indices is not None:
+        if os.environ.get("PNLP_FLASHMASK_KERNEL", "0") == "1":  # v1 FlashMask forced
+            return False
+        if startend_row_indices.dim() == 4 and startend_row_indices.shape[1] != 1:
+            return False
+    return True
+
+
+def packed_rope_attention(qkv, cos, sin, num_heads: int, num_kv_heads: int,
+                          startend_row_indices=None) -> torch.Tensor:
+    """Causal (optionally FlashMask) attention with rope on packed qkv
+    [B, S, (Hq + 2*Hk)*D]; cos/sin: [S, D].  Rotates qkv IN PLACE and returns
+    the attention output [B, S, Hq, D].  Call only where
+    packed_rope_attention_supported() holds."""
+    se = startend_row_indices
+    if se is not None:
+        if se.dim() == 4:
+            se = se[:, 0, :, 0]
+        se = se.contiguous()
+    _, o = _PackedRopeAttnFunction.apply(qkv, cos, sin, num_heads, num_kv_heads, se)
+    return o
 
 
 # ---------------------------------------------------------------------------

@@ -47,14 +47,19 @@ class LlamaRMSNorm(nn.Module):
             # (reference register_sequence_parallel_allreduce_hooks)
             self.weight.sequence_parallel = True
 
-    def forward(self, x):
-        out = ops.rms_norm(x, self.weight, self.eps)
+    def forward(self, x, delta=None):
+        """norm(x); with delta: (x + delta, norm(x + delta)) from one fused
+        kernel that also does the residual add."""
+        if delta is None:
+            h, out = None, ops.rms_norm(x, self.weight, self.eps)
+        else:
+            h, out = ops.add_rms_norm(x, delta, self.weight, self.eps)
         # outlier-suppression shift (llm/utils/quant.py apply_shift): the
         # following linears see shifted activations and compensate in bias
         shift = getattr(self, "shift_bias", None)
         if shift is not None:
             out = out + shift
-        return out
+        return out if delta is None else (h, out)
 
 
 class LlamaRotaryEmbedding(nn.Module):
@@ -156,6 +161,20 @@ class LlamaAttention(nn.Module):
             assert self.num_kv_heads_local % self.sep_degree == 0
             self.reshard = ReshardLayer()
 
+    def _packed_path(self, qkv, attn_mask, startend_row_indices, past_key_value, use_cache):
+        cfg = self.config
+        return (
+            ops.layer_fusion_enabled()
+            and cfg.use_fused_rope and cfg.use_fused_rms_norm and cfg.use_flash_attention
+            and cfg.tensor_parallel_degree <= 1
+            and self.sep_degree == 1 and self.cp_degree == 1
+            and past_key_value is None and not use_cache
+            and attn_mask is None
+            and self.head_dim == 128
+            and ops.packed_rope_attention_supported(
+                qkv, self.num_heads_local, self.num_kv_heads_local, startend_row_indices)
+        )
+
     def forward(
         self,
         hidden_states: torch.Tensor,  # [B, S, H]
@@ -170,6 +189,15 @@ class LlamaAttention(nn.Module):
 
         if self.config.fuse_attention_qkv:
             qkv = self.qkv_proj(hidden_states)
+            if self._packed_path(qkv, attn_mask, startend_row_indices,
+                                 past_key_value, use_cache):
+                # rope in place on the packed rows, attention through row
+                # strides: no split copies, no cat in backward
+                S = qkv.shape[1]
+                cos, sin = self.rotary_emb(S, qkv.device, position_offset)
+                attn_out = ops.packed_rope_attention(
+                    qkv, cos, sin, hl, kl, startend_row_indices)
+                return self.o_proj(attn_out.reshape(B, S, hl * d))
             q, k, v = qkv.split([hl * d, kl * d, kl * d], dim=-1)
         else:
             q = self.q_proj(hidden_states)
@@ -303,7 +331,12 @@ class LlamaDecoderLayer(nn.Module):
         past_key_value=None,
         use_cache=False,
         position_offset=0,
+        fused_residual=False,
+        pending_delta=None,
     ):
+        if fused_residual:
+            return self.forward_fused(hidden_states, pending_delta, attn_mask,
+                                      startend_row_indices, position_offset)
         residual = hidden_states
         hidden_states = self.input_layernorm(hidden_states)
         attn_out = self.self_attn(
@@ -320,6 +353,27 @@ class LlamaDecoderLayer(nn.Module):
         if use_cache:
             return hidden_states, present
         return hidden_states
+
+    def forward_fused(self, residual, delta, attn_mask=None,
+                      startend_row_indices=None, position_offset=0):
+        """The layer with its residual adds folded into the norms.
+
+        The hidden state enters as residual + delta with the add still
+        pending (delta None: nothing pending) and leaves the same way, so
+        every add runs inside the norm kernel that follows it: the attention
+        add in post_attention_layernorm, the MLP add in the next layer's
+        input_layernorm or the model's final norm.  Same values as forward().
+        Reached through forward(fused_residual=True) so module hooks run.
+        """
+        if delta is None:
+            hidden_states = self.input_layernorm(residual)
+        else:
+            residual, hidden_states = self.input_layernorm(residual, delta)
+        attn_out = self.self_attn(
+            hidden_states, attn_mask, startend_row_indices, None, False, position_offset,
+        )
+        residual, hidden_states = self.post_attention_layernorm(residual, attn_out)
+        return residual, self.mlp(hidden_states)
 
 
 class LlamaPretrainedModel(PretrainedModel):
@@ -448,6 +502,22 @@ class LlamaModel(LlamaPretrainedModel):
         position_offset = 0
         if past_key_values is not None and past_key_values[0] is not None:
             position_offset = past_key_values[0][0].shape[1]
+
+        # Fused residual stream: thread (residual, pending delta) through the
+        # layers so each add runs inside the following norm's kernel.  Layers
+        # called one at a time (recompute, use_cache, pipeline stages) keep
+        # the plain interface.
+        if (ops.layer_fusion_enabled() and self.config.use_fused_rms_norm
+                and not use_cache and past_key_values is None
+                and not (self.config.recompute and self.training)):
+            residual, delta = hidden_states, None
+            for layer in self.layers:
+                residual, delta = layer(
+                    residual, attn_mask, startend_row_indices, None, False,
+                    position_offset, fused_residual=True, pending_delta=delta)
+            if delta is None:
+                return self.norm(residual)
+            return self.norm(residual, delta)[1]
 
         presents = [] if use_cache else None
         for i, layer in enumerate(self.layers):
