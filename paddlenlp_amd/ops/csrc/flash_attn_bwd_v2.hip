@@ -1,8 +1,9 @@
 // FlashAttention-2 backward v2 — 8-wave 32x32 MFMA structure for gfx950.
 //
 // Same technique set as the v2 forward (flash_attn_v2.hip): 32x32x16
-// MFMA, XOR-swizzled LDS staging, async-stage split, in-register
-// P/dS-to-fragment conversion via permlane32_swap.
+// MFMA, tiles staged by LDS-DMA into dual-use LDS images (read by rows and
+// transposed, mfma.h img_off), in-register P/dS-to-fragment conversion via
+// permlane32_swap.
 //
 // The key structural choice: backward has NO online softmax — lse and
 // delta are precomputed arrays — so the C-layout orientation of the two
@@ -40,19 +41,20 @@ __global__ __launch_bounds__(FB2_BLOCK) void flash_bwd2_dq_kernel(
     ushort_t* __restrict__ dq, const int* __restrict__ startend,
     FlashStrides rs,   // row strides (elements) of q, k/v, dq; dout is contiguous
     int B, int Sq, int Skv, int Hq, int Hk, float scale, int causal) {
+    static_assert(D == 128, "the dual-use image is laid out for 128-column tiles");
     constexpr int BLKN = 64;
     constexpr int DSTEPS = D / 16;
     constexpr int NDT = D / 32;
     constexpr int BLKM = FB2_WAVES * 32;
 
-    // double-buffered (one barrier per KV tile; see flash_attn_v2.hip)
-    __shared__ ushort_t k_lds[2][BLKN * D];    // row-major [kv][d]
-    __shared__ ushort_t v_lds[2][BLKN * D];    // row-major [kv][d]
-    __shared__ ushort_t kt_lds[2][D * BLKN];   // transposed [d][kv]
-    __shared__ int se_lds[2][MASKED ? BLKN : 1];  // FlashMask bounds
+    // [buffer][0 = K, 1 = V] dual-use images filled by LDS-DMA, double-
+    // buffered with one barrier per KV tile; FlashMask bounds in three slots,
+    // filled two tiles ahead (see flash_attn_v2.hip)
+    __shared__ __attribute__((aligned(16))) ushort_t kv_lds[2][2][BLKN * D];
+    __shared__ int se_lds[3][MASKED ? BLKN : 1];
 
     const int tid = threadIdx.x;
-    const int wave = tid >> 6;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lane = tid & 63;
     const int l32 = lane & 31;
     const int hi = lane >> 5;
@@ -109,59 +111,87 @@ __global__ __launch_bounds__(FB2_BLOCK) void flash_bwd2_dq_kernel(
         n_kv_tiles = min(n_kv_tiles, max(lim, 0));
     }
 
-    const int s_rowp = tid >> 4;
-    const int s_col = (tid & 15) * 8;
-    const int s_row0 = s_rowp * 2;
-    short8v sk0, sk1, sv0, sv1;
-
-    auto load_tile = [&](int kv_base) {
-        int g0 = kv_base + s_row0;
-        sk0 = short8v{0,0,0,0,0,0,0,0}; sk1 = sk0; sv0 = sk0; sv1 = sk0;
-        if (g0 < Skv) {
-            sk0 = *reinterpret_cast<const short8v*>(k_ptr + (long long)g0 * kv_row_stride + s_col);
-            sv0 = *reinterpret_cast<const short8v*>(v_ptr + (long long)g0 * kv_row_stride + s_col);
-        }
-        if (g0 + 1 < Skv) {
-            sk1 = *reinterpret_cast<const short8v*>(k_ptr + (long long)(g0 + 1) * kv_row_stride + s_col);
-            sv1 = *reinterpret_cast<const short8v*>(v_ptr + (long long)(g0 + 1) * kv_row_stride + s_col);
-        }
-    };
-    auto write_tile = [&](int buf, int kv_base) {
-        if (MASKED && tid < BLKN) {
-            int g = kv_base + tid;
-            se_lds[buf][tid] =
-                (g < Skv) ? startend[(long long)b * Skv + g] : 0;
-        }
-        *reinterpret_cast<short8v*>(swz<D>(k_lds[buf], s_row0, s_col)) = sk0;
-        *reinterpret_cast<short8v*>(swz<D>(k_lds[buf], s_row0 + 1, s_col)) = sk1;
-        *reinterpret_cast<short8v*>(swz<D>(v_lds[buf], s_row0, s_col)) = sv0;
-        *reinterpret_cast<short8v*>(swz<D>(v_lds[buf], s_row0 + 1, s_col)) = sv1;
+    // DMA of the kv tile at kv_base into buffer buf: each wave fills image
+    // rows 8*wave .. +7 of K and of V (2 x 1 KiB each).  A ragged tile
+    // cannot be zero-filled by DMA: rows past Skv re-read row Skv-1 (finite
+    // data); the kvg < Skv visibility test makes P = 0 and dS = 0 there, so
+    // the clamped K rows are multiplied by exact zeros.  The launcher checks
+    // that the k/v bases and the row stride are 16-byte aligned.
+    auto issue_tile = [&](int kv_base, int buf) {
+        // recomputed per tile, not hoisted and spilled (see the dkv kernel)
+        const int ln = fresh_lane_id();
 #pragma unroll
-        for (int j = 0; j < 8; j++) {
-            unsigned p32 = ((unsigned)(unsigned short)sk0[j]) |
-                           (((unsigned)(unsigned short)sk1[j]) << 16);
-            *reinterpret_cast<unsigned*>(swz<BLKN>(kt_lds[buf], s_col + j, s_row0)) = p32;
+        for (int i = 0; i < 2; i++) {
+            const int piece = wave * 2 + i;
+            const int src_row = min(kv_base + img_fill_row(piece, ln), Skv - 1);
+            const long long off = (long long)src_row * kv_row_stride +
+                                  img_fill_chunk(piece, ln) * 8;
+            lds_dma16(k_ptr + off, &kv_lds[buf][0][piece * 512]);
+            lds_dma16(v_ptr + off, &kv_lds[buf][1][piece * 512]);
         }
     };
-
-    // per-wave bound reduce (see flash_attn_v2.hip tile_bounds)
-    auto tile_se_max = [&](int kv_base) -> int {
-        int g = kv_base + lane;
-        int v = (g < Skv) ? startend[(long long)b * Skv + g] : 0;
+    // FlashMask bounds of tile `tile` into slot tile % 3 (wave 0; columns
+    // past Skv repeat the last one: the max is unchanged and their
+    // kvg >= Skv test hides them)
+    auto issue_bounds = [&](int tile, int slot) {
+        if (MASKED && wave == 0) {
+            const int ln = fresh_lane_id();
+            lds_dma4(startend + (long long)b * Skv + min(tile * BLKN + ln, Skv - 1),
+                     &se_lds[slot][0]);
+        }
+    };
+    // per-wave max of a landed tile's 64 bounds, out of LDS
+    auto tile_se_max = [&](int slot) -> int {
+        int v = se_lds[slot][lane];
 #pragma unroll
         for (int off = 32; off; off >>= 1)
             v = max(v, __shfl_xor(v, off, 64));
-        return v;
+        return __builtin_amdgcn_readfirstlane(v);
     };
 
-    load_tile(0);
-    write_tile(0, 0);
-    int se_max_cur = MASKED ? tile_se_max(0) : 0x7fffffff;
-    __syncthreads();
+    // retire the stationary loads here: left pending, the compiler waits for
+    // them with a counted vmcnt inside the tile loop, and that count would
+    // also drain the (uncounted) DMA in flight
+#pragma unroll
+    for (int kk = 0; kk < DSTEPS; kk++)
+        asm volatile("" :: "v"(aq[kk]), "v"(ado[kk]));
+    asm volatile("" :: "v"(lse_q), "v"(dl_q));
+    if (n_kv_tiles > 0) {
+        issue_tile(0, 0);
+        issue_bounds(0, 0);
+        if (n_kv_tiles > 1) issue_bounds(1, 1);
+    }
+    int se_max_cur = 0x7fffffff;
+    int se_slot = 0;   // kvt % 3
 
     for (int kvt = 0; kvt < n_kv_tiles; kvt++) {
         const int kv_base = kvt * BLKN;
         const int cur = kvt & 1;
+        // tile kvt (and the bounds of kvt+1) have landed and every wave is
+        // done reading the other buffer, which tile kvt+1 now overwrites
+        // while tile kvt is computed
+        lds_dma_wait_all();
+        __syncthreads();
+        const int se_slot_next = (se_slot == 2) ? 0 : se_slot + 1;
+        if (MASKED && kvt == 0) se_max_cur = tile_se_max(0);
+        int se_max_next = 0x7fffffff;
+        if (kvt + 1 < n_kv_tiles) {
+            bool stage_skip = false;
+            if (MASKED) {
+                se_max_next = tile_se_max(se_slot_next);
+                // whole block past every bound: skip the K/V staging too
+                stage_skip = (q_base >= se_max_next);
+            }
+            if (!stage_skip) issue_tile(kv_base + BLKN, cur ^ 1);
+            // slot (kvt+2) % 3 was last read as tile kvt-1
+            if (kvt + 2 < n_kv_tiles)
+                issue_bounds(kvt + 2, (se_slot_next == 2) ? 0 : se_slot_next + 1);
+        }
+        const ushort_t* k_img = kv_lds[cur][0];
+        const ushort_t* v_img = kv_lds[cur][1];
+        const int lane_t = fresh_lane_id();   // for the transposed reads
+
+        // wave-uniform: the transposed reads below need EXEC all ones
         bool wave_skip =
             causal && (kv_base > qw + 31 + causal_off);
         // FlashMask whole-tile skip (see fwd): no bound exceeds this
@@ -177,10 +207,8 @@ __global__ __launch_bounds__(FB2_BLOCK) void flash_bwd2_dq_kernel(
             __builtin_amdgcn_s_setprio(1);
 #pragma unroll
             for (int kk = 0; kk < DSTEPS; kk++) {
-                frag8 ak = *reinterpret_cast<const frag8*>(
-                    swz<D>(k_lds[cur], sub * 32 + l32, kk * 16 + hi * 8));
-                frag8 av = *reinterpret_cast<const frag8*>(
-                    swz<D>(v_lds[cur], sub * 32 + l32, kk * 16 + hi * 8));
+                frag8 ak = img_row_frag(k_img, sub * 32 + l32, kk, hi);
+                frag8 av = img_row_frag(v_img, sub * 32 + l32, kk, hi);
                 st = mfma32(ak, aq[kk], st);
                 dp = mfma32(av, ado[kk], dp);
             }
@@ -194,13 +222,13 @@ __global__ __launch_bounds__(FB2_BLOCK) void flash_bwd2_dq_kernel(
                 int kvg = kv_base + row;
                 bool vis = (kvg < Skv) && (qg < Sq) &&
                            (!causal || kvg <= qg + causal_off);
-                if (MASKED) vis = vis && (qg < se_lds[cur][row]);
+                if (MASKED) vis = vis && (qg < se_lds[se_slot][row]);
                 float p = vis ? __expf(st[r] * scale - lse_q) : 0.f;
                 st[r] = p * (dp[r] - dl_q) * scale;  // = dS^T
             }
 
             // dQ += dS·K: A = T12(dS^T) (lane: dS[q=l32][kv-slice]),
-            // B = K[kv][d] column-slices from kt_lds
+            // B = K[kv][d] column slices: the K image read transposed
             __builtin_amdgcn_s_setprio(1);
 #pragma unroll
             for (int ksl = 0; ksl < 2; ksl++) {
@@ -208,31 +236,19 @@ __global__ __launch_bounds__(FB2_BLOCK) void flash_bwd2_dq_kernel(
                 frag8 ads = t12_convert(st, ksl * 8);
 #pragma unroll
                 for (int n = 0; n < NDT; n++) {
-                    frag8 bkf = *reinterpret_cast<const frag8*>(
-                        swz<BLKN>(kt_lds[cur], n * 32 + l32, ks * 16 + hi * 8));
+                    frag8 bkf = img_tr_frag(k_img, ks, n, lane_t);
                     acc_dq[n] = mfma32(ads, bkf, acc_dq[n]);
                 }
             }
             __builtin_amdgcn_s_setprio(0);
         };
 
-        if (!wave_skip) process_sub(0);
-        int se_max_next = 0x7fffffff;
-        bool stage_skip = false;
-        if (kvt + 1 < n_kv_tiles) {
-            if (MASKED) {
-                se_max_next = tile_se_max(kv_base + BLKN);
-                // whole block past every bound: skip the K/V staging too
-                stage_skip = (q_base >= se_max_next);
-            }
-            if (!stage_skip) load_tile(kv_base + BLKN);
+        if (!wave_skip) {
+            process_sub(0);
+            process_sub(1);
         }
-        if (!wave_skip) process_sub(1);
-
-        if (kvt + 1 < n_kv_tiles && !stage_skip)
-            write_tile(cur ^ 1, kv_base + BLKN);
         if (MASKED) se_max_cur = se_max_next;
-        __syncthreads();
+        se_slot = se_slot_next;
     }
 
     // epilogue: acc_dq C-layout [q][d] (col = d, row = q)
@@ -542,6 +558,11 @@ bool launch_flash_bwd2(const void* dout, const void* q, const void* k, const voi
                        const FlashStrides* strides) {
     if (D != 128 || (Hq % Hk) != 0) return false;
     const FlashStrides rs = strides ? *strides : flash_contiguous_strides(Hq, Hk, D);
+    // dq stages K and V, dkv stages Q and dO (contiguous) by LDS-DMA, which
+    // needs 16-byte aligned sources
+    if (!flash_dma_aligned(q, rs.q) || !flash_dma_aligned(k, rs.kv) ||
+        !flash_dma_aligned(v, rs.kv) || !flash_dma_aligned(dout, Hq * D))
+        return false;
     if (parts & FLASH_BWD_DELTA)
         launch_flash_bwd_delta(dout, o, delta, B, Sq, Hq, D, stream);
     if (parts & FLASH_BWD_DQ) {
@@ -572,6 +593,9 @@ bool launch_flash_bwd2_mask(const void* dout, const void* q, const void* k,
                             const FlashStrides* strides) {
     if (D != 128 || (Hq % Hk) != 0) return false;
     const FlashStrides rs = strides ? *strides : flash_contiguous_strides(Hq, Hk, D);
+    if (!flash_dma_aligned(q, rs.q) || !flash_dma_aligned(k, rs.kv) ||
+        !flash_dma_aligned(v, rs.kv) || !flash_dma_aligned(dout, Hq * D))
+        return false;
     launch_flash_bwd_delta(dout, o, delta, B, Sq, Hq, D, stream);
     dim3 gq((Sq + 255) / 256, B * Hq);
     hipLaunchKernelGGL((flash_bwd2_dq_kernel<128, true>), gq, dim3(FB2_BLOCK), 0, stream,

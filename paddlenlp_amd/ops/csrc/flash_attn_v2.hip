@@ -13,12 +13,13 @@
 //     two lane-halves.  (v1 spent 8 shfl_xor rounds per 4-row group.)
 //   * In-register P -> PV A-fragment conversion via packed bf16 +
 //     permlane32_swap (guide T12): no p_lds round trip at all.
-//   * K and V^T staged in XOR-swizzled LDS (guide T2/G4: row-major
-//     [*][128] bf16 read as column-slices is a 32-way bank conflict;
-//     byte ^= (row&7)<<4 spreads it across 8 slots).
-//   * Async-stage split (guide T14): next tile's global loads are issued
-//     before this tile's softmax+PV so ~500-cycle HBM latency hides under
-//     compute; ds_writes land after the barrier.
+//   * K and V staged by LDS-DMA into one dual-use LDS image each (mfma.h
+//     img_off): S^T reads the K image by rows (ds_read_b128), PV reads the
+//     V image transposed (ds_read_b64_tr_b16), so no V^T copy is written and
+//     no staging registers are held.  Tile t+1 is in flight into the other
+//     buffer while tile t is computed; one barrier per tile.  Measured
+//     against register staging with a transposing ds_write_b32 pass:
+//     profiles/fa_fwd_dq_lds_dma.md.
 //   * Defer-max rescale (guide T13, THR=8): O-rescale only runs when the
 //     running max actually grew, saving the per-tile O sweep.
 //   * s_setprio(1) around the MFMA clusters (guide T5).
@@ -81,27 +82,25 @@ __global__ __launch_bounds__(FA2_BLOCK) void flash_fwd2_kernel(
     const int* __restrict__ startend, // FlashMask [B, Skv] (MASKED only)
     FlashStrides rs,                  // row strides of q and k/v (elements)
     int B, int Sq, int Skv, int Hq, int Hk, float scale, int causal) {
+    static_assert(D == 128, "the dual-use image is laid out for 128-column tiles");
     constexpr int DSTEPS = D / 16;    // K-steps of the S^T MFMAs
     constexpr int NDT = D / 32;       // 32-col d-tiles of O
     constexpr int KVT = FA2_BLKN / 32;  // kv sub-tiles (2)
 
-    // double-buffered: compute tile t from buf[t&1] while staging t+1 into
-    // buf[(t+1)&1] -> ONE barrier per KV tile instead of two (the barrier
-    // drain before s_barrier is the dominant structural stall, guide §5)
-    __shared__ ushort_t k_lds[2][FA2_BLKN * D];
-    __shared__ ushort_t vt_lds[2][D * FA2_BLKN];
-    // per-tile FlashMask column bounds (staged with the K/V tile) and
-    // the tile's max bound (wave 0 reduces it during staging) for
-    // whole-tile skipping: a wave with qw >= max end sees nothing
-    // per-tile FlashMask column bounds (staged with the K/V tile);
-    // the tile min/max bounds travel in registers: every wave reduces
-    // the 64-int column itself (256 B from L2, 6 shfl_xor) one tile
-    // ahead, so whole-tile skips AND whole-block staging skips need no
-    // extra barrier
-    __shared__ int se_lds[2][MASKED ? FA2_BLKN : 1];
+    // [buffer][0 = K, 1 = V] dual-use images (mfma.h img_off), filled by
+    // LDS-DMA: tile t+1 lands in buf[(t+1)&1] while tile t is computed from
+    // buf[t&1], with ONE barrier per KV tile (the barrier drain before
+    // s_barrier is the dominant structural stall, guide §5)
+    __shared__ __attribute__((aligned(16))) ushort_t kv_lds[2][2][FA2_BLKN * D];
+    // per-tile FlashMask column bounds, filled by 4-byte LDS-DMA two tiles
+    // ahead (three slots): when tile t is computed the bounds of tile t+1
+    // have landed too, so every wave reduces them out of LDS (6 shfl_xor)
+    // for the whole-tile skip and the whole-block staging skip, and the
+    // tile loop holds no ordinary global load at all
+    __shared__ int se_lds[3][MASKED ? FA2_BLKN : 1];
 
     const int tid = threadIdx.x;
-    const int wave = tid >> 6;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lane = tid & 63;
     const int l32 = lane & 31;
     const int hi = lane >> 5;
@@ -158,66 +157,96 @@ __global__ __launch_bounds__(FA2_BLOCK) void flash_fwd2_kernel(
         n_kv_tiles = min(n_kv_tiles, max(lim, 0));
     }
 
-    // register staging: each thread owns 2 consecutive kv rows x 8 d cols
-    const int s_rowp = tid >> 4;              // 0..31 row pair
-    const int s_col = (tid & 15) * 8;         // d col (D=128: 16 chunks)
-    const int s_row0 = s_rowp * 2;
-    short8v sk0, sk1, sv0, sv1;
-
-    auto load_tile = [&](int kv_base) {
-        int g0 = kv_base + s_row0;
-        sk0 = short8v{0,0,0,0,0,0,0,0}; sk1 = sk0; sv0 = sk0; sv1 = sk0;
-        if (g0 < Skv) {
-            sk0 = *reinterpret_cast<const short8v*>(k_ptr + (long long)g0 * kv_row_stride + s_col);
-            sv0 = *reinterpret_cast<const short8v*>(v_ptr + (long long)g0 * kv_row_stride + s_col);
-        }
-        if (g0 + 1 < Skv) {
-            sk1 = *reinterpret_cast<const short8v*>(k_ptr + (long long)(g0 + 1) * kv_row_stride + s_col);
-            sv1 = *reinterpret_cast<const short8v*>(v_ptr + (long long)(g0 + 1) * kv_row_stride + s_col);
-        }
-    };
-    auto write_tile = [&](int buf, int kv_base) {
-        if (MASKED && tid < FA2_BLKN) {
-            int g = kv_base + tid;
-            se_lds[buf][tid] =
-                (g < Skv) ? startend[(long long)b * Skv + g] : 0;
-        }
-        *reinterpret_cast<short8v*>(swz<D>(k_lds[buf], s_row0, s_col)) = sk0;
-        *reinterpret_cast<short8v*>(swz<D>(k_lds[buf], s_row0 + 1, s_col)) = sk1;
+    // DMA of the kv tile at kv_base into buffer buf: each wave fills image
+    // rows 8*wave .. +7 of K and of V (2 x 1 KiB each).  A ragged tile
+    // cannot be zero-filled by DMA: rows past Skv re-read row Skv-1 (finite
+    // data); S is set to -inf for kvg >= Skv, so P = 0 there and the clamped
+    // V rows are multiplied by exact zeros.  The source must be 16-byte
+    // aligned: the launcher checks the k/v bases and the row stride, a head
+    // starts at a multiple of 256 bytes.
+    auto issue_tile = [&](int kv_base, int buf) {
+        // per-lane source offsets are recomputed every tile from a lane id
+        // the compiler cannot hoist: kept live across the loop they spill,
+        // and a scratch reload after the DMA issue would drain the prefetch
+        const int ln = fresh_lane_id();
 #pragma unroll
-        for (int j = 0; j < 8; j++) {
-            unsigned p32 = ((unsigned)(unsigned short)sv0[j]) |
-                           (((unsigned)(unsigned short)sv1[j]) << 16);
-            *reinterpret_cast<unsigned*>(swz<FA2_BLKN>(vt_lds[buf], s_col + j, s_row0)) = p32;
+        for (int i = 0; i < 2; i++) {
+            const int piece = wave * 2 + i;
+            const int src_row = min(kv_base + img_fill_row(piece, ln), Skv - 1);
+            const long long off = (long long)src_row * kv_row_stride +
+                                  img_fill_chunk(piece, ln) * 8;
+            lds_dma16(k_ptr + off, &kv_lds[buf][0][piece * 512]);
+            lds_dma16(v_ptr + off, &kv_lds[buf][1][piece * 512]);
         }
     };
-
-    // every wave reduces a tile's 64 bounds itself: returns (min, max)
-    // uniform across the wave, no shared-memory round trip
-    auto tile_bounds = [&](int kv_base, int& mn_out) -> int {
-        int g = kv_base + lane;
-        int v = (g < Skv) ? startend[(long long)b * Skv + g] : 0;
-        int mx = v, mn = (g < Skv) ? v : 0x7fffffff;
+    // FlashMask bounds of tile `tile` into slot tile % 3 (wave 0; columns
+    // past Skv repeat the last one, which changes neither min nor max, and
+    // their kvg >= Skv test hides them)
+    auto issue_bounds = [&](int tile, int slot) {
+        if (MASKED && wave == 0) {
+            const int ln = fresh_lane_id();
+            lds_dma4(startend + (long long)b * Skv + min(tile * FA2_BLKN + ln, Skv - 1),
+                     &se_lds[slot][0]);
+        }
+    };
+    // every wave reduces a landed tile's 64 bounds itself: returns (min,
+    // max) uniform across the wave
+    auto tile_bounds = [&](int slot, int& mn_out) -> int {
+        int mx = se_lds[slot][lane], mn = mx;
 #pragma unroll
         for (int off = 32; off; off >>= 1) {
             mx = max(mx, __shfl_xor(mx, off, 64));
             mn = min(mn, __shfl_xor(mn, off, 64));
         }
-        mn_out = mn;
-        return mx;
+        mn_out = __builtin_amdgcn_readfirstlane(mn);
+        return __builtin_amdgcn_readfirstlane(mx);
     };
 
-    load_tile(0);
-    write_tile(0, 0);
+    // retire the Q fragment loads here: left pending, the compiler waits for
+    // them with a counted vmcnt inside the tile loop, and that count would
+    // also drain the (uncounted) DMA in flight
+#pragma unroll
+    for (int kk = 0; kk < DSTEPS; kk++) asm volatile("" :: "v"(aq[kk]));
+    if (n_kv_tiles > 0) {
+        issue_tile(0, 0);
+        issue_bounds(0, 0);
+        if (n_kv_tiles > 1) issue_bounds(1, 1);
+    }
     int se_min_cur = 0, se_max_cur = 0x7fffffff;
-    if (MASKED) se_max_cur = tile_bounds(0, se_min_cur);
-    __syncthreads();
+    int se_slot = 0;   // kvt % 3
 
     for (int kvt = 0; kvt < n_kv_tiles; kvt++) {
         const int kv_base = kvt * FA2_BLKN;
         const int cur = kvt & 1;
+        // tile kvt (and the bounds of kvt+1) have landed (the compiler does
+        // not count the DMA, hence the explicit wait) and every wave is done
+        // reading the other buffer, which tile kvt+1 now overwrites while
+        // tile kvt is computed
+        lds_dma_wait_all();
+        __syncthreads();
+        const int se_slot_next = (se_slot == 2) ? 0 : se_slot + 1;
+        if (MASKED && kvt == 0) se_max_cur = tile_bounds(0, se_min_cur);
+        // FlashMask: when the whole BLOCK's first q row clears the next
+        // tile's max bound, nothing will read it: skip the 32 KB K/V stage
+        int se_min_next = 0, se_max_next = 0x7fffffff;
+        if (kvt + 1 < n_kv_tiles) {
+            bool stage_skip = false;
+            if (MASKED) {
+                se_max_next = tile_bounds(se_slot_next, se_min_next);
+                stage_skip = (q_base >= se_max_next);
+            }
+            if (!stage_skip) issue_tile(kv_base + FA2_BLKN, cur ^ 1);
+            // slot (kvt+2) % 3 was last read as tile kvt-1
+            if (kvt + 2 < n_kv_tiles)
+                issue_bounds(kvt + 2, (se_slot_next == 2) ? 0 : se_slot_next + 1);
+        }
+        const ushort_t* k_img = kv_lds[cur][0];
+        const ushort_t* v_img = kv_lds[cur][1];
+        const int lane_t = fresh_lane_id();   // for the transposed reads
+
         // a wave whose q rows all precede this kv tile contributes nothing:
-        // skip its compute but keep it in the staging barriers
+        // skip its compute but keep it in the staging and the barriers.
+        // Wave-uniform: the transposed reads below need EXEC all ones.
         bool wave_skip =
             causal && (kv_base > qw + FA2_QW - 1 + causal_off);
         // FlashMask whole-tile skip: every kv bound in this tile is at or
@@ -235,29 +264,12 @@ __global__ __launch_bounds__(FA2_BLOCK) void flash_fwd2_kernel(
             for (int kk = 0; kk < DSTEPS; kk++) {
 #pragma unroll
                 for (int nt = 0; nt < KVT; nt++) {
-                    frag8 ak = *reinterpret_cast<const frag8*>(
-                        swz<D>(k_lds[cur], nt * 32 + l32, kk * 16 + hi * 8));
+                    frag8 ak = img_row_frag(k_img, nt * 32 + l32, kk, hi);
                     st[nt] = mfma32(ak, aq[kk], st[nt]);
                 }
             }
             __builtin_amdgcn_s_setprio(0);
-        }
 
-        // issue next tile's global loads now (T14): latency hides under
-        // softmax + PV.  FlashMask: when the whole BLOCK's first q row
-        // clears the next tile's max bound, nothing will read it — skip
-        // the 32 KB K/V stage entirely (the bounds cost 256 B from L2)
-        int se_min_next = 0, se_max_next = 0x7fffffff;
-        bool stage_skip = false;
-        if (kvt + 1 < n_kv_tiles) {
-            if (MASKED) {
-                se_max_next = tile_bounds(kv_base + FA2_BLKN, se_min_next);
-                stage_skip = (q_base >= se_max_next);
-            }
-            if (!stage_skip) load_tile(kv_base + FA2_BLKN);
-        }
-
-        if (!wave_skip) {
             // mask + scale.  A tile is "full" when every (q, kv) pair in this
             // wave's sub-block is visible — the common case away from the
             // diagonal; masking math is skipped entirely.
@@ -279,7 +291,7 @@ __global__ __launch_bounds__(FA2_BLOCK) void flash_fwd2_kernel(
                         int kvg = kv_base + row;
                         bool vis = (kvg < Skv) &&
                                    (!causal || kvg <= qg + causal_off);
-                        if (MASKED) vis = vis && (qg < se_lds[cur][row]);
+                        if (MASKED) vis = vis && (qg < se_lds[se_slot][row]);
                         st[nt][r] = vis ? st[nt][r] * scale : -INFINITY;
                     }
             }
@@ -347,22 +359,15 @@ __global__ __launch_bounds__(FA2_BLOCK) void flash_fwd2_kernel(
                 frag8 pa = t12_convert(st[ks >> 1], (ks & 1) * 8);
 #pragma unroll
                 for (int n = 0; n < NDT; n++) {
-                    frag8 bv = *reinterpret_cast<const frag8*>(
-                        swz<FA2_BLKN>(vt_lds[cur], n * 32 + l32, ks * 16 + hi * 8));
+                    frag8 bv = img_tr_frag(v_img, ks, n, lane_t);
                     acc_o[n] = mfma32(pa, bv, acc_o[n]);
                 }
             }
             __builtin_amdgcn_s_setprio(0);
         }
 
-        // stage t+1 into the OTHER buffer while this tile's compute may
-        // still be in flight on other waves, then one barrier: it both
-        // publishes buf[cur^1] and guarantees every wave has finished
-        // reading buf[cur] before iteration t+1 overwrites it
-        if (kvt + 1 < n_kv_tiles && !stage_skip)
-            write_tile(cur ^ 1, kv_base + FA2_BLKN);
         if (MASKED) { se_max_cur = se_max_next; se_min_cur = se_min_next; }
-        __syncthreads();
+        se_slot = se_slot_next;
     }
 
     // epilogue: O / l, LSE.  inv_l lives in the lane that owns q; O rows
@@ -402,6 +407,8 @@ bool launch_flash_fwd2(const void* q, const void* k, const void* v, void* o,
                        const FlashStrides* strides) {
     if (D != 128 || (Hq % Hk) != 0) return false;
     const FlashStrides rs = strides ? *strides : flash_contiguous_strides(Hq, Hk, D);
+    // K and V tiles are staged by LDS-DMA, which needs 16-byte aligned sources
+    if (!flash_dma_aligned(k, rs.kv) || !flash_dma_aligned(v, rs.kv)) return false;
     dim3 grid((Sq + FA2_BLKM - 1) / FA2_BLKM, B * Hq);
     hipLaunchKernelGGL((flash_fwd2_kernel<128, false>), grid, dim3(FA2_BLOCK), 0, stream,
                        (const ushort_t*)q, (const ushort_t*)k, (const ushort_t*)v,
@@ -417,6 +424,7 @@ bool launch_flash_fwd2_mask(const void* q, const void* k, const void* v,
                             const FlashStrides* strides) {
     if (D != 128 || (Hq % Hk) != 0) return false;
     const FlashStrides rs = strides ? *strides : flash_contiguous_strides(Hq, Hk, D);
+    if (!flash_dma_aligned(k, rs.kv) || !flash_dma_aligned(v, rs.kv)) return false;
     dim3 grid((Sq + FA2_BLKM - 1) / FA2_BLKM, B * Hq);
     hipLaunchKernelGGL((flash_fwd2_kernel<128, true>), grid, dim3(FA2_BLOCK), 0,
                        stream, (const ushort_t*)q, (const ushort_t*)k,

@@ -5,6 +5,7 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include <cstdint>
 #include <stdexcept>
 #include <string>
 
@@ -104,6 +105,13 @@ inline FlashStrides flash_contiguous_strides(int Hq, int Hk, int D) {
 inline FlashStrides flash_packed_strides(int Hq, int Hk, int D) {
     int w = (Hq + 2 * Hk) * D;
     return {w, w, w, w};
+}
+// The v2 kernels stage tiles by LDS-DMA in 16-byte pieces: a tensor staged
+// that way needs a 16-byte aligned base and a row stride that is a multiple
+// of 8 bf16 elements (a head starts at a multiple of D * 2 = 256 bytes).
+// The launchers decline anything else, like a shape that is not theirs.
+inline bool flash_dma_aligned(const void* p, int row_stride) {
+    return reinterpret_cast<uintptr_t>(p) % 16 == 0 && row_stride % 8 == 0;
 }
 void launch_mfma32_probe(const void* A, const void* B, float* C, hipStream_t stream);
 void launch_permlane_probe(int* out0, int* out1, hipStream_t stream);
