@@ -195,6 +195,15 @@ class FusedMultiTransformer(nn.Module):
     k_scales = None  # set by allocate_caches(cachekv_dtype="int8")
     v_scales = None
     tp_group = None  # set by from_llama(tp_degree > 1): row-parallel reduce
+    # Routed FFN: "auto" takes the fused sync-free kernels (ops.moe_ffn) for
+    # GPU inputs they support, up to moe_fused_max_tokens tokens; "torch"
+    # always runs the capacity-padded torch formulation.
+    moe_impl: str = "auto"
+    # Measured (tools/bench_moe.py, profiles/moe_ffn.md, one Mixtral-8x7B
+    # layer): fused / torch = 3.9x at T = 1, 1.6-1.9x at T = 4..64, 1.3x at
+    # T = 256.  No crossover up to 256, the largest T measured, and the ratio
+    # is falling, so the limit stays there.
+    moe_fused_max_tokens: int = 256
 
     def __init__(self, config: FusedMultiTransformerConfig):
         super().__init__()
@@ -455,6 +464,15 @@ class FusedMultiTransformer(nn.Module):
         T = x.shape[0]
         E, K = c.moe_num_experts, c.moe_top_k
         router = x @ self.moe_gates[i].t()
+        if self.moe_impl not in ("auto", "torch"):
+            raise ValueError(f"moe_impl must be 'auto' or 'torch', got {self.moe_impl!r}")
+        if (self.moe_impl == "auto" and x.is_cuda and T <= self.moe_fused_max_tokens
+                and ops.moe_ffn_supported(x, router, self.moe_w1[i], self.moe_w3[i],
+                                          self.moe_w2[i], K)):
+            # on-device routing + grouped GEMMs over the selected experts
+            # only; no host sync, so the decode step stays capturable
+            return ops.moe_ffn(x, router, self.moe_w1[i], self.moe_w3[i],
+                               self.moe_w2[i], K).reshape(shp)
         probs = router.float().softmax(-1)
         topw, tope = probs.topk(K, dim=-1)
         topw = (topw / topw.sum(-1, keepdim=True)).to(x.dtype)

@@ -9,6 +9,9 @@ from .functional import (  # noqa: F401
     flash_attention,
     fused_adamw,
     fused_rope,
+    moe_ffn,
+    moe_ffn_supported,
+    moe_route,
     rms_norm,
     swiglu,
 )

@@ -800,6 +800,113 @@ torch::Tensor wint8_gemv(torch::Tensor x, torch::Tensor wq, torch::Tensor scale)
     return y;
 }
 
+// ---- moe_ffn.hip ----
+static void check_moe_route_args(const torch::Tensor& logits, int64_t top_k) {
+    CHECK_GPU(logits); CHECK_CONTIG(logits);
+    TORCH_CHECK(logits.dim() == 2, "router logits must be [T, E]");
+    TORCH_CHECK(logits.scalar_type() == torch::kFloat32 ||
+                logits.scalar_type() == torch::kBFloat16,
+                "router logits must be fp32 or bf16");
+    TORCH_CHECK(logits.size(1) >= 1 && logits.size(1) <= kMoeMaxExperts,
+                "moe: at most ", kMoeMaxExperts, " experts");
+    TORCH_CHECK(top_k >= 1 && top_k <= kMoeMaxTopK && top_k <= logits.size(1),
+                "moe: top_k must be in 1..min(E, ", kMoeMaxTopK, ")");
+}
+
+std::vector<torch::Tensor> moe_route(torch::Tensor logits, int64_t top_k) {
+    check_moe_route_args(logits, top_k);
+    const int T = logits.size(0), E = logits.size(1), K = (int)top_k;
+    auto ids = torch::empty({(long)T, (long)K}, logits.options().dtype(torch::kInt32));
+    auto w = torch::empty({(long)T, (long)K}, logits.options().dtype(torch::kFloat32));
+    launch_moe_route(logits.data_ptr(), logits.scalar_type() == torch::kBFloat16,
+                     ids.data_ptr<int>(), w.data_ptr<float>(), T, E, K, cur_stream());
+    return {ids, w};
+}
+
+// topk_ids [T, K] int32 -> sorted_rows [P], tile_expert [P / 32], row_pos
+// [T, K], num_tiles [1]
+std::vector<torch::Tensor> moe_align(torch::Tensor topk_ids, int64_t num_experts) {
+    CHECK_GPU(topk_ids); CHECK_CONTIG(topk_ids);
+    TORCH_CHECK(topk_ids.dim() == 2 && topk_ids.scalar_type() == torch::kInt32,
+                "topk_ids must be [T, K] int32");
+    const int T = topk_ids.size(0), K = topk_ids.size(1), E = (int)num_experts;
+    TORCH_CHECK(E >= 1 && E <= kMoeMaxExperts, "moe: at most ", kMoeMaxExperts, " experts");
+    TORCH_CHECK((long)T * K <= kMoeMaxFlatRows, "moe: T * top_k must be <= ",
+                kMoeMaxFlatRows);
+    const long P = moe_padded_rows(T, K, E);
+    auto opt = topk_ids.options();
+    auto sorted_rows = torch::empty({P}, opt);
+    auto tile_expert = torch::empty({P / kMoeRowTile}, opt);
+    auto row_pos = torch::empty({(long)T, (long)K}, opt);
+    auto num_tiles = torch::empty({1}, opt);
+    launch_moe_align(topk_ids.data_ptr<int>(), sorted_rows.data_ptr<int>(),
+                     tile_expert.data_ptr<int>(), row_pos.data_ptr<int>(),
+                     num_tiles.data_ptr<int>(), T, K, E, cur_stream());
+    return {sorted_rows, tile_expert, row_pos, num_tiles};
+}
+
+static bool aligned16(const torch::Tensor& t) {
+    return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+}
+
+torch::Tensor moe_ffn(torch::Tensor x, torch::Tensor router_logits, torch::Tensor w1,
+                      torch::Tensor w3, torch::Tensor w2, int64_t top_k) {
+    CHECK_GPU(x); CHECK_CONTIG(x); CHECK_BF16(x);
+    CHECK_GPU(w1); CHECK_CONTIG(w1); CHECK_BF16(w1);
+    CHECK_GPU(w3); CHECK_CONTIG(w3); CHECK_BF16(w3);
+    CHECK_GPU(w2); CHECK_CONTIG(w2); CHECK_BF16(w2);
+    check_moe_route_args(router_logits, top_k);
+    TORCH_CHECK(x.dim() == 2 && w1.dim() == 3 && w3.dim() == 3 && w2.dim() == 3,
+                "moe_ffn: x [T, H], w1/w3 [E, H, I], w2 [E, I, H]");
+    const int T = x.size(0), H = x.size(1);
+    const int E = w1.size(0), I = w1.size(2), K = (int)top_k;
+    TORCH_CHECK(router_logits.size(0) == T && router_logits.size(1) == E,
+                "moe_ffn: router logits must be [T, E]");
+    TORCH_CHECK(w1.size(1) == H && w3.sizes() == w1.sizes() && w2.size(0) == E &&
+                w2.size(1) == I && w2.size(2) == H,
+                "moe_ffn: w1/w3 [E, H, I], w2 [E, I, H]");
+    TORCH_CHECK(H % 128 == 0 && I % 128 == 0,
+                "moe_ffn: H and I must be multiples of 128");
+    TORCH_CHECK((long)T * K <= kMoeMaxFlatRows, "moe_ffn: T * top_k must be <= ",
+                kMoeMaxFlatRows);
+    // LDS-DMA sources: 16-byte aligned bases (rows are multiples of 256 bytes)
+    TORCH_CHECK(aligned16(x) && aligned16(w1) && aligned16(w3) && aligned16(w2),
+                "moe_ffn: x and the weights must be 16-byte aligned");
+    auto out = torch::empty({(long)T, (long)H}, x.options());
+    if (T == 0) return out;
+
+    auto stream = cur_stream();
+    auto i32 = x.options().dtype(torch::kInt32);
+    auto f32 = x.options().dtype(torch::kFloat32);
+    const long P = moe_padded_rows(T, K, E);
+    const int ks = moe_down_ksplit(T, K, H, I);
+    auto ids = torch::empty({(long)T, (long)K}, i32);
+    auto topw = torch::empty({(long)T, (long)K}, f32);
+    auto sorted_rows = torch::empty({P}, i32);
+    auto tile_expert = torch::empty({P / kMoeRowTile}, i32);
+    auto row_pos = torch::empty({(long)T, (long)K}, i32);
+    auto num_tiles = torch::empty({1}, i32);
+    auto zero_row = torch::zeros({(long)H}, x.options());
+    auto act = torch::empty({P, (long)I}, x.options());
+    auto partial = torch::empty({(long)ks, P, (long)H}, f32);
+
+    launch_moe_route(router_logits.data_ptr(),
+                     router_logits.scalar_type() == torch::kBFloat16,
+                     ids.data_ptr<int>(), topw.data_ptr<float>(), T, E, K, stream);
+    launch_moe_align(ids.data_ptr<int>(), sorted_rows.data_ptr<int>(),
+                     tile_expert.data_ptr<int>(), row_pos.data_ptr<int>(),
+                     num_tiles.data_ptr<int>(), T, K, E, stream);
+    launch_moe_gate_up(x.data_ptr(), zero_row.data_ptr(), w1.data_ptr(), w3.data_ptr(),
+                       sorted_rows.data_ptr<int>(), tile_expert.data_ptr<int>(),
+                       num_tiles.data_ptr<int>(), act.data_ptr(), T, K, E, H, I, stream);
+    launch_moe_down(act.data_ptr(), w2.data_ptr(), tile_expert.data_ptr<int>(),
+                    num_tiles.data_ptr<int>(), partial.data_ptr<float>(), ks,
+                    T, K, E, H, I, stream);
+    launch_moe_combine(partial.data_ptr<float>(), row_pos.data_ptr<int>(),
+                       topw.data_ptr<float>(), out.data_ptr(), ks, T, K, E, H, stream);
+    return out;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("rms_norm_fwd", &rms_norm_fwd);
     m.def("rms_norm_bwd", &rms_norm_bwd);
@@ -859,4 +966,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("fp8_rowwise_quant", &fp8_rowwise_quant);
     m.def("skinny_gemm", &skinny_gemm, py::arg("x"), py::arg("w"),
           py::arg("ksplit") = 8);
+    m.def("moe_route", &moe_route, py::arg("logits"), py::arg("top_k"));
+    m.def("moe_align", &moe_align, py::arg("topk_ids"), py::arg("num_experts"));
+    m.def("moe_ffn", &moe_ffn, py::arg("x"), py::arg("router_logits"),
+          py::arg("w1"), py::arg("w3"), py::arg("w2"), py::arg("top_k"));
+    m.def("moe_down_ksplit", &moe_down_ksplit);
 }

@@ -199,6 +199,41 @@ int skinny_gemm_ksplit(int N, int K, int ksplit_req);
 void launch_skinny_gemm(const void* x, const void* w, float* partial, void* y,
                         int M, int N, int K, int ksplit, hipStream_t stream);
 
+// ---- moe_ffn.hip: routed FFN over stacked expert weights [E, K, N].  Every
+// grid depends on shapes only; nothing syncs with the host. ----
+constexpr int kMoeRowTile = 32;     // MT: rows of one grouped-GEMM tile
+constexpr int kMoeMaxExperts = 64;
+constexpr int kMoeMaxTopK = 8;
+constexpr int kMoeMaxFlatRows = 4096;   // T * K the align kernel takes
+// P = roundup(T*K + E*(MT-1), MT): rows of the expert-sorted, tile-padded batch
+int moe_padded_rows(int T, int K, int E);
+int moe_down_ksplit(int T, int K, int H, int I);
+// logits [T, E] fp32 or bf16 -> topk_ids [T, K], topk_w [T, K] (softmax over
+// E, top-k, renormalised; ties go to the lower expert index)
+void launch_moe_route(const void* logits, bool logits_bf16, int* topk_ids,
+                      float* topk_w, int T, int E, int K, hipStream_t stream);
+// sorted_rows [P] (flat row t*K + k, -1 = padding), tile_expert [P/MT],
+// row_pos [T, K] (inverse of sorted_rows), num_tiles [1]
+void launch_moe_align(const int* topk_ids, int* sorted_rows, int* tile_expert,
+                      int* row_pos, int* num_tiles, int T, int K, int E,
+                      hipStream_t stream);
+// act_sorted [P, I] = silu(x @ w1[e]) * (x @ w3[e]) per row tile; zero_row
+// holds H bf16 zeros (the source of padding rows).  H % 128 == I % 128 == 0,
+// all bases 16-byte aligned.
+void launch_moe_gate_up(const void* x, const void* zero_row, const void* w1,
+                        const void* w3, const int* sorted_rows,
+                        const int* tile_expert, const int* num_tiles,
+                        void* act_sorted, int T, int K, int E, int H, int I,
+                        hipStream_t stream);
+// partial [ksplit, P, H] fp32, ksplit = moe_down_ksplit(...)
+void launch_moe_down(const void* act_sorted, const void* w2,
+                     const int* tile_expert, const int* num_tiles,
+                     float* partial, int ksplit, int T, int K, int E, int H,
+                     int I, hipStream_t stream);
+void launch_moe_combine(const float* partial, const int* row_pos,
+                        const float* topk_w, void* out, int ksplit, int T,
+                        int K, int E, int H, hipStream_t stream);
+
 // ---- sampling.hip ----
 void launch_repetition_penalty(void* logits, const long long* pre_ids,
                                const int* pre_lens, const float* rep_pen,

@@ -312,7 +312,11 @@ __global__ void rope_cache_append_kernel(
 
     const ushort_t* src = qkv + (((long long)b * T + t) * H_all + head) * D;
     constexpr int half = D / 2;
-    constexpr int EPL = half / 64;  // rotation pairs per lane
+    // rotation pairs per lane.  D = 64 has 32 pairs: lanes 0..31 take one
+    // each and the upper half of the wave idles (half / 64 would be zero
+    // pairs: q_out left at zero and no K written).
+    constexpr int EPL = (half + 63) / 64;
+    const bool pair_lane = lane * EPL < half;
 
     bool is_q = head < Hq;
     bool is_k = head >= Hq && head < Hq + Hk;
@@ -320,22 +324,28 @@ __global__ void rope_cache_append_kernel(
     if (is_q || is_k) {
         const float* cr = cos_t + (long long)pos * D;
         const float* sr = sin_t + (long long)pos * D;
-        float o1[EPL > 0 ? EPL : 1], o2[EPL > 0 ? EPL : 1];
+        float o1[EPL], o2[EPL];
 #pragma unroll
         for (int e = 0; e < EPL; e++) {
             int i = lane * EPL + e;
-            float a = bf16_to_f32(src[i]);
-            float bb = bf16_to_f32(src[i + half]);
-            o1[e] = a * cr[i] - bb * sr[i];
-            o2[e] = bb * cr[i + half] + a * sr[i + half];
+            o1[e] = 0.f;
+            o2[e] = 0.f;
+            if (pair_lane) {
+                float a = bf16_to_f32(src[i]);
+                float bb = bf16_to_f32(src[i + half]);
+                o1[e] = a * cr[i] - bb * sr[i];
+                o2[e] = bb * cr[i + half] + a * sr[i + half];
+            }
         }
         if (is_q) {
             ushort_t* dst = q_out + (((long long)b * T + t) * Hq + head) * D;
 #pragma unroll
             for (int e = 0; e < EPL; e++) {
                 int i = lane * EPL + e;
-                dst[i] = f32_to_bf16(o1[e]);
-                dst[i + half] = f32_to_bf16(o2[e]);
+                if (pair_lane) {
+                    dst[i] = f32_to_bf16(o1[e]);
+                    dst[i + half] = f32_to_bf16(o2[e]);
+                }
             }
         } else {
             int hk = head - Hq;
@@ -354,8 +364,10 @@ __global__ void rope_cache_append_kernel(
 #pragma unroll
                 for (int e = 0; e < EPL; e++) {
                     int i = lane * EPL + e;
-                    dst[i] = (signed char)lrintf(fminf(fmaxf(o1[e] / sc, -127.f), 127.f));
-                    dst[i + half] = (signed char)lrintf(fminf(fmaxf(o2[e] / sc, -127.f), 127.f));
+                    if (pair_lane) {
+                        dst[i] = (signed char)lrintf(fminf(fmaxf(o1[e] / sc, -127.f), 127.f));
+                        dst[i + half] = (signed char)lrintf(fminf(fmaxf(o2[e] / sc, -127.f), 127.f));
+                    }
                 }
                 if (lane == 0) k_scale[tok] = sc;
             } else if (MODE == 2) {
@@ -386,8 +398,10 @@ __global__ void rope_cache_append_kernel(
 #pragma unroll
                 for (int e = 0; e < EPL; e++) {
                     int i = lane * EPL + e;
-                    dst[i] = f32_to_bf16(o1[e]);
-                    dst[i + half] = f32_to_bf16(o2[e]);
+                    if (pair_lane) {
+                        dst[i] = f32_to_bf16(o1[e]);
+                        dst[i + half] = f32_to_bf16(o2[e]);
+                    }
                 }
             }
         }

@@ -381,3 +381,69 @@ def fused_adamw(
             masters[i] if masters is not None else None,
             lr, beta1, beta2, eps, weight_decay, step,
         )
+
+
+# ---------------------------------------------------------------------------
+# Routed MoE FFN (moe_ffn.hip): on-device routing + grouped MFMA GEMMs
+# ---------------------------------------------------------------------------
+MOE_MAX_EXPERTS = 64
+MOE_MAX_TOP_K = 8
+MOE_MAX_FLAT_ROWS = 4096   # T * top_k the alignment kernel takes
+
+
+def _moe_route_supported(logits: torch.Tensor, top_k: int) -> bool:
+    return (logits.is_cuda and logits.dim() == 2
+            and logits.dtype in (torch.float32, torch.bfloat16)
+            and 1 <= logits.shape[1] <= MOE_MAX_EXPERTS
+            and 1 <= top_k <= min(MOE_MAX_TOP_K, logits.shape[1]))
+
+
+def moe_ffn_supported(x: torch.Tensor, router_logits: torch.Tensor, w1: torch.Tensor,
+                      w3: torch.Tensor, w2: torch.Tensor, top_k: int) -> bool:
+    """True when the fused kernels take these arguments: bf16 x and contiguous
+    bf16 weights on the GPU, H and I multiples of 128, 16-byte aligned bases
+    (the LDS-DMA source requirement), E <= 64, top_k <= 8, T * top_k <= 4096."""
+    if not (x.is_cuda and x.dim() == 2 and w1.dim() == 3 and w2.dim() == 3):
+        return False
+    T, H = x.shape
+    E, _, I = w1.shape
+    if not _moe_route_supported(router_logits, top_k):
+        return False
+    if tuple(router_logits.shape) != (T, E) or T * top_k > MOE_MAX_FLAT_ROWS:
+        return False
+    if H % 128 or I % 128:
+        return False
+    if w1.shape != (E, H, I) or w3.shape != (E, H, I) or w2.shape != (E, I, H):
+        return False
+    for t in (x, w1, w3, w2):
+        if t.dtype != torch.bfloat16 or not t.is_cuda:
+            return False
+    for w in (w1, w3, w2):
+        if not w.is_contiguous() or w.data_ptr() % 16:
+            return False
+    return True
+
+
+def moe_route(logits: torch.Tensor, top_k: int):
+    """Router logits [T, E] -> (expert ids [T, K] int32, weights [T, K] fp32):
+    fp32 softmax over E, top-k, renormalised.  Ties go to the lower expert
+    index (reference.moe_route)."""
+    if _moe_route_supported(logits, top_k):
+        C = _load_extension()
+        ids, w = C.moe_route(logits.contiguous(), top_k)
+        return ids, w
+    return reference.moe_route(logits, top_k)
+
+
+def moe_ffn(x: torch.Tensor, router_logits: torch.Tensor, w1: torch.Tensor,
+            w3: torch.Tensor, w2: torch.Tensor, top_k: int) -> torch.Tensor:
+    """Routed SwiGLU FFN over stacked expert weights (w1/w3 [E, H, I], w2
+    [E, I, H]); x [T, H] -> [T, H] in x.dtype.  On the GPU path nothing syncs
+    with the host and only the selected experts' weights are read."""
+    if moe_ffn_supported(x, router_logits, w1, w3, w2, top_k):
+        C = _load_extension()
+        xc = x.contiguous()
+        if xc.data_ptr() % 16:
+            xc = xc.clone()
+        return C.moe_ffn(xc, router_logits.contiguous(), w1, w3, w2, top_k)
+    return reference.moe_ffn(x, router_logits, w1, w3, w2, top_k).to(x.dtype)

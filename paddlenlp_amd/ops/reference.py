@@ -80,6 +80,44 @@ def swiglu(x: torch.Tensor, y: Optional[torch.Tensor] = None) -> torch.Tensor:
     return F.silu(x) * y
 
 
+def moe_route(logits: torch.Tensor, top_k: int):
+    """Router: fp32 softmax over all E experts, top-k, then the k weights
+    renormalised to sum to 1.  logits [T, E] -> (ids [T, K] int32, weights
+    [T, K] fp32), in descending-probability order.
+
+    Tie rule (the same as the moe_route kernel's): among equal probabilities
+    the LOWER expert index wins.  A stable descending sort gives exactly that;
+    torch.topk leaves the order of ties unspecified."""
+    probs = logits.float().softmax(-1)
+    sp, si = torch.sort(probs, dim=-1, descending=True, stable=True)
+    w = sp[:, :top_k]
+    return si[:, :top_k].to(torch.int32), w / w.sum(-1, keepdim=True)
+
+
+def moe_ffn(x: torch.Tensor, router_logits: torch.Tensor, w1: torch.Tensor,
+            w3: torch.Tensor, w2: torch.Tensor, top_k: int) -> torch.Tensor:
+    """Routed SwiGLU FFN, fp32 math on whatever dtype it is given; returns
+    fp32 [T, H].  x [T, H], router_logits [T, E], w1/w3 [E, H, I], w2
+    [E, I, H]:
+
+        out[t] = sum_k w[t,k] * (silu(x[t] @ w1[e]) * (x[t] @ w3[e])) @ w2[e],
+        (e, w) = moe_route(router_logits, top_k)[t, k]
+
+    Only the selected experts are visited, so an unselected expert's weights
+    may hold anything (NaN included).  The k contributions are added in k
+    order."""
+    ids, w = moe_route(router_logits, top_k)
+    x32 = x.float()
+    out = torch.zeros_like(x32)
+    for k in range(top_k):
+        for e in torch.unique(ids[:, k]).tolist():
+            rows = (ids[:, k] == e).nonzero(as_tuple=True)[0]
+            xe = x32[rows]
+            act = F.silu(xe @ w1[e].float()) * (xe @ w3[e].float())
+            out[rows] += (act @ w2[e].float()) * w[rows, k, None]
+    return out
+
+
 def flash_attention(
     q: torch.Tensor,  # [B, S, Hq, D]
     k: torch.Tensor,  # [B, S, Hk, D]
