@@ -97,14 +97,20 @@ std::vector<torch::Tensor> add_rms_norm_bwd(torch::Tensor dy, torch::Tensor dh,
 std::vector<torch::Tensor> rope_fwd(torch::Tensor q, torch::Tensor k,
                                     torch::Tensor cos_t, torch::Tensor sin_t,
                                     bool backward) {
-    CHECK_GPU(q); CHECK_CONTIG(q); CHECK_BF16(q); CHECK_CONTIG(k); CHECK_BF16(k);
+    CHECK_GPU(q); CHECK_CONTIG(q); CHECK_BF16(q);
+    CHECK_GPU(k); CHECK_CONTIG(k); CHECK_BF16(k);
+    CHECK_GPU(cos_t); CHECK_GPU(sin_t);
     TORCH_CHECK(q.dim() == 4 && k.dim() == 4, "q/k must be [B,S,H,D]");
     int B = q.size(0), S = q.size(1), Hq = q.size(2), D = q.size(3);
     int Hk = k.size(2);
+    TORCH_CHECK(k.size(0) == B && k.size(1) == S && k.size(3) == D,
+                "k must agree with q in B, S and D");
     TORCH_CHECK(D % 8 == 0, "head dim must be a multiple of 8");
     auto cf = cos_t.to(torch::kFloat32).contiguous();
     auto sf = sin_t.to(torch::kFloat32).contiguous();
-    TORCH_CHECK(cf.size(0) == S && cf.size(-1) == D, "cos table must be [S, D]");
+    TORCH_CHECK(cf.size(0) == S && cf.size(-1) == D && cf.numel() == (int64_t)S * D &&
+                    sf.sizes() == cf.sizes(),
+                "cos/sin tables must be [S, D]");
     auto q_out = torch::empty_like(q);
     auto k_out = torch::empty_like(k);
     launch_rope(q.data_ptr(), q_out.data_ptr(), cf.data_ptr<float>(), sf.data_ptr<float>(),
@@ -151,8 +157,14 @@ torch::Tensor swiglu_fwd(torch::Tensor x) {
 
 torch::Tensor swiglu_bwd(torch::Tensor dy, torch::Tensor x) {
     CHECK_GPU(dy); CHECK_CONTIG(dy); CHECK_BF16(dy);
+    CHECK_GPU(x); CHECK_CONTIG(x); CHECK_BF16(x);
     int twoI = x.size(-1);
+    TORCH_CHECK(twoI % 16 == 0, "last dim must be a multiple of 16");
     int I = twoI / 2;
+    auto dy_sizes = x.sizes().vec();
+    dy_sizes.back() = I;
+    TORCH_CHECK(dy.sizes() == c10::IntArrayRef(dy_sizes),
+                "dy must be shaped like x with half the last dim");
     long long N = x.numel() / twoI;
     auto dx = torch::empty_like(x);
     launch_swiglu_bwd(dy.data_ptr(), x.data_ptr(), dx.data_ptr(), N, I, cur_stream());
@@ -167,8 +179,10 @@ std::vector<torch::Tensor> cross_entropy_fwd(torch::Tensor logits, torch::Tensor
     long long N = logits.size(0);
     int V = logits.size(1);
     TORCH_CHECK(V % 8 == 0, "vocab must be a multiple of 8");
+    CHECK_GPU(labels);
+    TORCH_CHECK(labels.numel() == N, "labels must have one entry per row");
     auto labels64 = labels.to(torch::kInt64).contiguous();
-    auto loss = torch::empty({N}, logits.options().dtype(torch::kFloat32));
+    auto loss =torch::empty({N}, logits.options().dtype(torch::kFloat32));
     auto maxlse = torch::empty({N, 2}, logits.options().dtype(torch::kFloat32));
     launch_ce_fwd(logits.data_ptr(), reinterpret_cast<const long long*>(labels64.data_ptr<int64_t>()),
                   loss.data_ptr<float>(), maxlse.data_ptr<float>(), N, V,
@@ -180,8 +194,17 @@ torch::Tensor cross_entropy_bwd(torch::Tensor dloss, torch::Tensor logits,
                                 torch::Tensor labels, torch::Tensor maxlse,
                                 int64_t ignore_index) {
     CHECK_GPU(dloss);
+    CHECK_GPU(logits); CHECK_CONTIG(logits); CHECK_BF16(logits);
+    TORCH_CHECK(logits.dim() == 2, "logits must be [N, V]");
     long long N = logits.size(0);
     int V = logits.size(1);
+    TORCH_CHECK(V % 8 == 0, "vocab must be a multiple of 8");
+    CHECK_GPU(labels); CHECK_GPU(maxlse);
+    TORCH_CHECK(labels.numel() == N, "labels must have one entry per row");
+    TORCH_CHECK(dloss.numel() == N, "dloss must have one entry per row");
+    TORCH_CHECK(maxlse.scalar_type() == torch::kFloat32 && maxlse.is_contiguous() &&
+                    maxlse.dim() == 2 && maxlse.size(0) == N && maxlse.size(1) == 2,
+                "maxlse must be the contiguous fp32 [N, 2] the forward returned");
     auto labels64 = labels.to(torch::kInt64).contiguous();
     auto dl = dloss.to(torch::kFloat32).contiguous();
     auto dlogits = torch::empty_like(logits);
@@ -561,23 +584,46 @@ void fused_adamw(std::vector<torch::Tensor> params, std::vector<torch::Tensor> g
                  int64_t step) {
     TORCH_CHECK(!params.empty());
     bool has_master = !masters.empty();
+    TORCH_CHECK(grads.size() == params.size() && exp_avgs.size() == params.size() &&
+                    exp_avg_sqs.size() == params.size() &&
+                    (!has_master || masters.size() == params.size()),
+                "params, grads, exp_avgs, exp_avg_sqs and masters must have the same length");
     const long long CHUNK = 1 << 22;  // 4M elements per chunk
     std::vector<AdamWChunk> chunks;
+    // gradients converted to the param's dtype or layout; the chunk table
+    // points into them, so they live until after the launch
+    std::vector<torch::Tensor> held_grads;
+    auto check_state = [](const torch::Tensor& t, const torch::Tensor& p, const char* what) {
+        TORCH_CHECK(t.is_cuda() && t.device() == p.device() && t.is_contiguous() &&
+                        t.scalar_type() == torch::kFloat32 && t.numel() == p.numel(),
+                    what, " must be a contiguous fp32 GPU tensor of the param's numel");
+    };
     for (size_t i = 0; i < params.size(); i++) {
         auto& p = params[i];
         CHECK_GPU(p); CHECK_CONTIG(p);
         bool is_bf16 = p.scalar_type() == torch::kBFloat16;
+        TORCH_CHECK(is_bf16 || p.scalar_type() == torch::kFloat32,
+                    "params must be bf16 or fp32");
+        TORCH_CHECK(p.device() == params[0].device(), "params must be on one device");
         TORCH_CHECK(!is_bf16 || has_master, "bf16 params need master weights");
         long long n = p.numel();
+        check_state(exp_avgs[i], p, "exp_avg");
+        check_state(exp_avg_sqs[i], p, "exp_avg_sq");
+        if (has_master && is_bf16) check_state(masters[i], p, "master");
         torch::Tensor g = grads[i];
-        if (g.scalar_type() != p.scalar_type()) g = g.to(p.scalar_type());
+        TORCH_CHECK(g.is_cuda() && g.device() == p.device() && g.numel() == n,
+                    "grad must be a GPU tensor of the param's numel");
+        if (g.scalar_type() != p.scalar_type() || !g.is_contiguous()) {
+            g = g.to(p.scalar_type()).contiguous();
+            held_grads.push_back(g);
+        }
         for (long long off = 0; off < n; off += CHUNK) {
             AdamWChunk c;
             c.param = p.data_ptr();
             c.grad = g.data_ptr();
             c.m = exp_avgs[i].data_ptr<float>();
             c.v = exp_avg_sqs[i].data_ptr<float>();
-            c.master = has_master ? masters[i].data_ptr<float>() : nullptr;
+            c.master = is_bf16 ? masters[i].data_ptr<float>() : nullptr;
             c.offset = off;
             c.n = std::min(CHUNK, n - off);
             c.is_bf16 = is_bf16 ? 1 : 0;

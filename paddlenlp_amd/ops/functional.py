@@ -326,7 +326,10 @@ class _CrossEntropyFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, labels, ignore_index):
         C = _load_extension()
-        loss, lse = C.cross_entropy_fwd(logits.contiguous(), labels, ignore_index)
+        # the backward reads the saved logits with a row stride of V, so it
+        # gets the contiguous tensor the forward ran on, not the caller's view
+        logits = logits.contiguous()
+        loss, lse = C.cross_entropy_fwd(logits, labels, ignore_index)
         ctx.save_for_backward(logits, labels, lse)
         ctx.ignore_index = ignore_index
         return loss

@@ -107,9 +107,10 @@ def test_rope_fwd_bwd(C):
     assert torch.allclose(k1.float(), k2, atol=2e-2, rtol=2e-2)
     dq = torch.randn_like(q1)
     dk = torch.randn_like(k1)
-    (q1 * dq).sum().backward()
-    (q2 * dq.float()).sum().backward()
+    ((q1 * dq).sum() + (k1 * dk).sum()).backward()
+    ((q2 * dq.float()).sum() + (k2 * dk.float()).sum()).backward()
     assert torch.allclose(q.grad.float(), qr.grad, atol=2e-2, rtol=2e-2)
+    assert torch.allclose(k.grad.float(), kr.grad, atol=2e-2, rtol=2e-2)
 
 
 def test_swiglu_fwd_bwd(C):
