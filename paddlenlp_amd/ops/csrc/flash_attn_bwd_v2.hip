@@ -21,6 +21,17 @@
 //
 // v1 (flash_attn.hip) staged P^T/dS^T through LDS between every GEMM
 // pair; measured A/B at the bench shape: v1 191 TF/s -> v2 (this file).
+//
+// Softmax recompute (mfma.h, profiles/fa_softmax_diet.md): both kernels
+// take a wave-uniform full-tile path per 32 x 32 sub-block with no compare
+// and no select; the masked path (diagonal, ragged and FlashMask boundary
+// tiles) selects masked pairs to exact zeros after the arithmetic.  P and dS
+// are rounded exactly as before (fma, mul, exp, sub, mul, mul per score), so
+// dq, dk and dv keep their bits; no packed f32 VALU; bf16 pairs packed by one
+// v_cvt_pk_bf16_f32; the dkv kernel reads lse and delta 16 bytes at a time.
+// (Starting the chains from the row constants and moving the scale of dS to
+// the epilogue is faster still but moves the last place of dS, and with it
+// the benchmark's outputs: not used.)
 #include "launchers.h"
 #include "mfma.h"
 
@@ -140,13 +151,17 @@ __global__ __launch_bounds__(FB2_BLOCK) void flash_bwd2_dq_kernel(
                      &se_lds[slot][0]);
         }
     };
-    // per-wave max of a landed tile's 64 bounds, out of LDS
-    auto tile_se_max = [&](int slot) -> int {
-        int v = se_lds[slot][lane];
+    // per-wave (min, max) of a landed tile's 64 bounds, out of LDS: the max
+    // drives the skips, the min the full-tile test
+    auto tile_bounds = [&](int slot, int& mn_out) -> int {
+        int mx = se_lds[slot][lane], mn = mx;
 #pragma unroll
-        for (int off = 32; off; off >>= 1)
-            v = max(v, __shfl_xor(v, off, 64));
-        return __builtin_amdgcn_readfirstlane(v);
+        for (int off = 32; off; off >>= 1) {
+            mx = max(mx, __shfl_xor(mx, off, 64));
+            mn = min(mn, __shfl_xor(mn, off, 64));
+        }
+        mn_out = __builtin_amdgcn_readfirstlane(mn);
+        return __builtin_amdgcn_readfirstlane(mx);
     };
 
     // retire the stationary loads here: left pending, the compiler waits for
@@ -161,7 +176,7 @@ __global__ __launch_bounds__(FB2_BLOCK) void flash_bwd2_dq_kernel(
         issue_bounds(0, 0);
         if (n_kv_tiles > 1) issue_bounds(1, 1);
     }
-    int se_max_cur = 0x7fffffff;
+    int se_min_cur = 0, se_max_cur = 0x7fffffff;
     int se_slot = 0;   // kvt % 3
 
     for (int kvt = 0; kvt < n_kv_tiles; kvt++) {
@@ -173,12 +188,12 @@ __global__ __launch_bounds__(FB2_BLOCK) void flash_bwd2_dq_kernel(
         lds_dma_wait_all();
         __syncthreads();
         const int se_slot_next = (se_slot == 2) ? 0 : se_slot + 1;
-        if (MASKED && kvt == 0) se_max_cur = tile_se_max(0);
-        int se_max_next = 0x7fffffff;
+        if (MASKED && kvt == 0) se_max_cur = tile_bounds(0, se_min_cur);
+        int se_min_next = 0, se_max_next = 0x7fffffff;
         if (kvt + 1 < n_kv_tiles) {
             bool stage_skip = false;
             if (MASKED) {
-                se_max_next = tile_se_max(se_slot_next);
+                se_max_next = tile_bounds(se_slot_next, se_min_next);
                 // whole block past every bound: skip the K/V staging too
                 stage_skip = (q_base >= se_max_next);
             }
@@ -215,16 +230,32 @@ __global__ __launch_bounds__(FB2_BLOCK) void flash_bwd2_dq_kernel(
             __builtin_amdgcn_s_setprio(0);
 
             // P^T = exp(S^T*scale - lse_q); dS^T = P^T*(dP^T - delta_q)*
-            // scale (all per-lane: q = l32)
+            // scale (all per-lane: q = l32), rounded as before.  When every
+            // (q, kv) pair of this 32 x 32 sub-block is visible, the common
+            // case away from the diagonal, there is no compare and no
+            // select.  On the other path a masked pair is selected to an
+            // exact 0 after the arithmetic, whatever its row's lse (-inf for
+            // a row without keys, +inf past Sq) made of the exponent.
+            const int kv_sub = kv_base + sub * 32;
+            const bool full_sub =
+                (kv_sub + 32 <= Skv) && (qw + 31 < Sq) &&
+                (!causal || (kv_sub + 31 <= qw + causal_off)) &&
+                (!MASKED || (qw + 31 < se_min_cur));
 #pragma unroll
             for (int r = 0; r < 16; r++) {
-                int row = sub * 32 + crow32(r, hi);
-                int kvg = kv_base + row;
-                bool vis = (kvg < Skv) && (qg < Sq) &&
-                           (!causal || kvg <= qg + causal_off);
-                if (MASKED) vis = vis && (qg < se_lds[se_slot][row]);
-                float p = vis ? __expf(st[r] * scale - lse_q) : 0.f;
-                st[r] = p * (dp[r] - dl_q) * scale;  // = dS^T
+                float p = __expf(__builtin_fmaf(st[r], scale, -lse_q));
+                st[r] = sm_opaque(p * (dp[r] - dl_q) * scale);  // = dS^T
+            }
+            if (!full_sub) {
+#pragma unroll
+                for (int r = 0; r < 16; r++) {
+                    int row = sub * 32 + crow32(r, hi);
+                    int kvg = kv_base + row;
+                    bool vis = (kvg < Skv) && (qg < Sq) &&
+                               (!causal || kvg <= qg + causal_off);
+                    if (MASKED) vis = vis && (qg < se_lds[se_slot][row]);
+                    st[r] = vis ? st[r] : 0.f;
+                }
             }
 
             // dQ += dS·K: A = T12(dS^T) (lane: dS[q=l32][kv-slice]),
@@ -247,7 +278,7 @@ __global__ __launch_bounds__(FB2_BLOCK) void flash_bwd2_dq_kernel(
             process_sub(0);
             process_sub(1);
         }
-        if (MASKED) se_max_cur = se_max_next;
+        if (MASKED) { se_max_cur = se_max_next; se_min_cur = se_min_next; }
         se_slot = se_slot_next;
     }
 
@@ -293,7 +324,7 @@ __global__ __launch_bounds__(FB2_BLOCK, 1) void flash_bwd2_dkv_kernel(
 
     // [buffer][0 = Q, 1 = dO] dual-use images, [buffer][0 = lse, 1 = delta]
     __shared__ __attribute__((aligned(16))) ushort_t qd_lds[2][2][BLKQ * D];
-    __shared__ float ld_lds[2][2][BLKQ];
+    __shared__ __attribute__((aligned(16))) float ld_lds[2][2][BLKQ];
 
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -317,15 +348,21 @@ __global__ __launch_bounds__(FB2_BLOCK, 1) void flash_bwd2_dkv_kernel(
     __shared__ int blk_max_lds[MASKED ? FB2_WAVES : 1];
     int kv_end_lane = 0x7fffffff;
     int wave_max_end = 0x7fffffff;
+    int wave_min_end = 0x7fffffff;   // q rows below it clear every bound: full-tile test
     if (MASKED) {
         kv_end_lane = (kvg_lane < Skv)
             ? startend[(long long)b * Skv + kvg_lane] : 0;
         wave_max_end = kv_end_lane;
+        wave_min_end = kv_end_lane;
 #pragma unroll
-        for (int off = 32; off; off >>= 1)
+        for (int off = 32; off; off >>= 1) {
             wave_max_end = max(wave_max_end,
                                __shfl_xor(wave_max_end, off, 64));
+            wave_min_end = min(wave_min_end,
+                               __shfl_xor(wave_min_end, off, 64));
+        }
         wave_max_end = __builtin_amdgcn_readfirstlane(wave_max_end);
+        wave_min_end = __builtin_amdgcn_readfirstlane(wave_min_end);
         if (lane == 0) blk_max_lds[wave] = wave_max_end;
     }
 
@@ -431,7 +468,6 @@ __global__ __launch_bounds__(FB2_BLOCK, 1) void flash_bwd2_dkv_kernel(
         const int q_tb = qt * BLKQ;
         const ushort_t* q_img = qd_lds[cur][0];
         const ushort_t* do_img = qd_lds[cur][1];
-        const int lane_t = fresh_lane_id();   // for the transposed reads
         // skip q tiles fully below this wave's causal diagonal, or
         // (FlashMask) entirely past every bound this wave holds.  Wave-
         // uniform: the transposed reads below need EXEC all ones.
@@ -458,37 +494,71 @@ __global__ __launch_bounds__(FB2_BLOCK, 1) void flash_bwd2_dkv_kernel(
                 __builtin_amdgcn_s_setprio(0);
 
                 // P = exp(S*scale - lse[q]) overwrites S; dS = P*(dP -
-                // delta[q])*scale overwrites dP.  Rows are q (wave-
-                // uniform per reg): lse/delta broadcast from LDS.
+                // delta[q])*scale overwrites dP, rounded as before.  Rows are
+                // q, and registers 4g .. 4g+3 hold rows 8g + 4*hi .. +3
+                // (crow32): one 16-byte LDS read each of lse and delta per g.
+                // When every (q, kv) pair of this 32 x 32 sub-block is visible
+                // there is no compare and no select.  On the other path a
+                // masked pair is selected to an exact 0 after the arithmetic,
+                // whatever its row's lse (-inf for a row without keys, whose
+                // pairs are all masked) made of the exponent: every value
+                // that survives the select was computed from finite numbers.
+                const int q_sub = q_tb + sub * 32;
+                const bool full_sub =
+                    (q_sub + 32 <= Sq) && (kvw + 32 <= Skv) &&
+                    (!causal || (kvw + 31 <= q_sub + causal_off)) &&
+                    (!MASKED || (q_sub + 31 < wave_min_end));
 #pragma unroll
-                for (int r = 0; r < 16; r++) {
-                    int qrow = sub * 32 + crow32(r, hi);
-                    int qgl = q_tb + qrow;
-                    float ls = ld_lds[cur][0][qrow];
-                    float dl = ld_lds[cur][1][qrow];
-                    bool vis = (qgl < Sq) && (kvg_lane < Skv) &&
-                               (!causal || kvg_lane <= qgl + causal_off);
-                    if (MASKED) vis = vis && (qgl < kv_end_lane);
-                    float p = (vis && ls != INFINITY)
-                                  ? __expf(st[r] * scale - ls) : 0.f;
-                    st[r] = p;
-                    dp[r] = p * (dp[r] - dl) * scale;  // dS
+                for (int g = 0; g < 4; g++) {
+                    const int row0 = sub * 32 + 8 * g + 4 * hi;
+                    const f32x4 ls4 = *reinterpret_cast<const f32x4*>(&ld_lds[cur][0][row0]);
+                    const f32x4 dl4 = *reinterpret_cast<const f32x4*>(&ld_lds[cur][1][row0]);
+#pragma unroll
+                    for (int j = 0; j < 4; j++) {
+                        const int r = 4 * g + j;
+                        float p = sm_opaque(__expf(__builtin_fmaf(st[r], scale, -ls4[j])));
+                        st[r] = p;
+                        dp[r] = sm_opaque(p * (dp[r] - dl4[j]) * scale);  // dS
+                    }
+                }
+                if (!full_sub) {
+#pragma unroll
+                    for (int r = 0; r < 16; r++) {
+                        int qgl = q_sub + crow32(r, hi);
+                        bool vis = (qgl < Sq) && (kvg_lane < Skv) &&
+                                   (!causal || kvg_lane <= qgl + causal_off);
+                        if (MASKED) vis = vis && (qgl < kv_end_lane);
+                        st[r] = vis ? st[r] : 0.f;
+                        dp[r] = vis ? dp[r] : 0.f;
+                    }
                 }
 
                 // dV += P^T·dO, dK += dS^T·Q (contract q: the 2
                 // k-steps of this sub-tile)
+                // All four A fragments are packed before the first MFMA, so
+                // the 32 f32 registers of P and dS are dead (16 packed ones
+                // live) while the transposed operands are read: this kernel
+                // sits at the register cap.
+                frag8 apt[2], ads[2];
+#pragma unroll
+                for (int ksl = 0; ksl < 2; ksl++) {
+                    apt[ksl] = t12_convert(st, ksl * 8);
+                    ads[ksl] = t12_convert(dp, ksl * 8);
+                }
+                asm volatile("" : "+v"(apt[0]), "+v"(apt[1]), "+v"(ads[0]), "+v"(ads[1]));
+                // the lane id of the transposed reads, re-derived here so that
+                // it is not live across the S and dP chains
+                const int lane_t = fresh_lane_id();
                 __builtin_amdgcn_s_setprio(1);
 #pragma unroll
                 for (int ksl = 0; ksl < 2; ksl++) {
                     const int ks = sub * 2 + ksl;
-                    frag8 apt = t12_convert(st, ksl * 8);
-                    frag8 ads = t12_convert(dp, ksl * 8);
 #pragma unroll
                     for (int n = 0; n < NDT; n++) {
                         frag8 bdo = img_tr_frag(do_img, ks, n, lane_t);
                         frag8 bq = img_tr_frag(q_img, ks, n, lane_t);
-                        acc_dv[n] = mfma32(apt, bdo, acc_dv[n]);
-                        acc_dk[n] = mfma32(ads, bq, acc_dk[n]);
+                        acc_dv[n] = mfma32(apt[ksl], bdo, acc_dv[n]);
+                        acc_dk[n] = mfma32(ads[ksl], bq, acc_dk[n]);
                     }
                 }
                 __builtin_amdgcn_s_setprio(0);

@@ -20,6 +20,15 @@
 //     buffer while tile t is computed; one barrier per tile.  Measured
 //     against register staging with a transposing ds_write_b32 pass:
 //     profiles/fa_fwd_dq_lds_dma.md.
+//   * Softmax VALU diet (mfma.h, profiles/fa_softmax_diet.md): scale > 0, so
+//     the row max is taken over the RAW scores (v_max3_f32 pairs) and scaled
+//     once per lane; a masked score (-inf) gives exp(-inf) = 0 without a
+//     test; on a fully visible tile nothing is compared or selected per
+//     score; no packed f32 VALU.  Every value is rounded as before, so o and
+//     lse keep their bits.  (An exp2-domain form with the scale folded into
+//     one fma per score is faster still but moves the last place of P, and
+//     the 32-layer bf16 model turns that into percents of the logits: not
+//     used.)
 //   * Defer-max rescale (guide T13, THR=8): O-rescale only runs when the
 //     running max actually grew, saving the per-tile O sweep.
 //   * s_setprio(1) around the MFMA clusters (guide T5).
@@ -270,19 +279,19 @@ __global__ __launch_bounds__(FA2_BLOCK) void flash_fwd2_kernel(
             }
             __builtin_amdgcn_s_setprio(0);
 
-            // mask + scale.  A tile is "full" when every (q, kv) pair in this
-            // wave's sub-block is visible — the common case away from the
-            // diagonal; masking math is skipped entirely.
+            // the MFMA results may now be read by sm_max3 (mfma.h); the fence
+            // names every S tile, so a third one must be added here too
+            static_assert(KVT == 2, "sm_fence below covers exactly two S tiles");
+            sm_fence(st[0], st[1]);
+
+            // mask, on RAW scores.  A tile is "full" when every (q, kv) pair
+            // in this wave's sub-block is visible, the common case away from
+            // the diagonal: no compare and no select at all.
             const bool full_tile =
                 (kv_base + FA2_BLKN <= Skv) &&
                 (!causal || (kv_base + FA2_BLKN - 1 <= qw + causal_off)) &&
                 (!MASKED || (qw + FA2_QW - 1 < se_min_cur));
-            if (full_tile) {
-#pragma unroll
-                for (int nt = 0; nt < KVT; nt++)
-#pragma unroll
-                    for (int r = 0; r < 16; r++) st[nt][r] *= scale;
-            } else {
+            if (!full_tile) {
 #pragma unroll
                 for (int nt = 0; nt < KVT; nt++)
 #pragma unroll
@@ -292,16 +301,18 @@ __global__ __launch_bounds__(FA2_BLOCK) void flash_fwd2_kernel(
                         bool vis = (kvg < Skv) &&
                                    (!causal || kvg <= qg + causal_off);
                         if (MASKED) vis = vis && (qg < se_lds[se_slot][row]);
-                        st[nt][r] = vis ? st[nt][r] * scale : -INFINITY;
+                        st[nt][r] = vis ? st[nt][r] : -INFINITY;
                     }
             }
 
-            // per-lane row max over the 32 kv values + one half-swap combine
+            // per-lane row max over the 32 kv values (v_max3 pairs) + one
+            // half-swap combine.  scale > 0 and rounding is monotone, so the
+            // max of the scaled scores is the scaled max of the raw ones: one
+            // multiply per lane, not one per score, and the same bits.
             float pm = -INFINITY;
 #pragma unroll
-            for (int nt = 0; nt < KVT; nt++)
-#pragma unroll
-                for (int r = 0; r < 16; r++) pm = fmaxf(pm, st[nt][r]);
+            for (int nt = 0; nt < KVT; nt++) pm = sm_tile_max(pm, st[nt]);
+            pm *= scale;
             {
                 union { float f; unsigned u; } x{pm};
                 auto rr = __builtin_amdgcn_permlane32_swap(x.u, x.u, false, false);
@@ -309,7 +320,10 @@ __global__ __launch_bounds__(FA2_BLOCK) void flash_fwd2_kernel(
                 pm = fmaxf(a.f, c.f);
             }
 
-            // defer-max (T13): only rescale O when the max actually grew
+            // defer-max (T13): only rescale O when the max actually grew.
+            // The decision comes before this tile's P is formed and after the
+            // previous tile's P.V is complete, and alpha scales l_run and O
+            // together.
             bool grew = pm > m_run + DEFER_THR ||
                         (m_run == -INFINITY && pm > -INFINITY);
             if (__any(grew)) {
@@ -330,14 +344,21 @@ __global__ __launch_bounds__(FA2_BLOCK) void flash_fwd2_kernel(
                 }
             }
 
-            // P = exp(S - m); per-lane sum + half-swap combine
+            // P = exp(S*scale - m), rounded exactly as before (the product,
+            // the difference and the exponent's log2(e) multiply each round
+            // once: sm_opaque keeps the product out of an fma), so o and lse
+            // keep their bits.  A masked score is -inf and gives exp(-inf) =
+            // 0 by itself, with no test per score.  A row that has seen no
+            // key yet (all its scores so far are -inf, the wave is not
+            // skipped because of its other rows) takes an effective max of
+            // 0, once per tile per lane: -inf - -inf would be NaN.
+            const float m_eff = (m_run == -INFINITY) ? 0.f : m_run;
             float ps = 0.f;
 #pragma unroll
             for (int nt = 0; nt < KVT; nt++)
 #pragma unroll
                 for (int r = 0; r < 16; r++) {
-                    float s = st[nt][r];
-                    float p = (s == -INFINITY) ? 0.f : __expf(s - m_run);
+                    float p = sm_opaque(__expf(sm_opaque(st[nt][r] * scale) - m_eff));
                     st[nt][r] = p;
                     ps += p;
                 }

@@ -36,6 +36,47 @@ __device__ __forceinline__ int crow32(int r, int hi) {
     return (r & 3) + 8 * (r >> 2) + 4 * hi;
 }
 
+// ---------------------------------------------------------------------------
+// Softmax arithmetic helpers of the v2 attention kernels.
+//
+// Next to MFMAs a packed f32 VALU instruction costs more than the two plain
+// ones it replaces, and under -O3 the SLP vectoriser packs adjacent
+// multiplies, adds and fmas of a tile into v_pk_*_f32.  It builds its packs
+// backwards from a vector's elements, and an element that comes out of an asm
+// statement is where it stops: sm_opaque(x) is x behind an EMPTY asm
+// statement (no instruction is emitted, so the compiler still schedules and
+// pads every real instruction itself).  It also keeps a product a product:
+// the optimiser cannot contract it into an fma with a later add, which would
+// round differently.
+//
+// fmaxf on an MFMA result gets a canonicalising v_max_f32 x, x, x in front,
+// so the forward's row max is taken with sm_max3, a real instruction in an
+// asm statement.  The compiler does not model what is inside one and pads no
+// hazard for it: sm_fence() holds the wait states an MFMA result needs before
+// a VALU instruction may read it (12 after an 8-pass MFMA) and must stand
+// between the MFMA chain that wrote a tile and the first sm_max3 that reads
+// it.  The reader depends on the fence's output, so it is not scheduled above
+// it.  The result of sm_max3 goes to compiler-visible instructions only.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ float sm_opaque(float x) {
+    asm("" : "+v"(x));
+    return x;
+}
+__device__ __forceinline__ void sm_fence(f32x16& a, f32x16& b) {
+    asm volatile("s_nop 11" : "+v"(a), "+v"(b));
+}
+__device__ __forceinline__ float sm_max3(float a, float b, float c) {
+    float d;
+    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
+    return d;
+}
+// max over the 16 registers of a C tile, as 8 v_max3_f32
+__device__ __forceinline__ float sm_tile_max(float m, const f32x16& s) {
+#pragma unroll
+    for (int r = 0; r < 16; r += 2) m = sm_max3(m, s[r], s[r + 1]);
+    return m;
+}
+
 // XOR swizzle for a row-major bf16 LDS tile (stride LD elements): a tile
 // read as column slices is a 32-way bank conflict; byte offset ^
 // ((row&7)<<4) spreads each column over 8 distinct 16-byte slots.  It is
@@ -47,8 +88,15 @@ __device__ __forceinline__ char* swz(ushort_t* base, int row, int col_elem) {
            (((row * LD + col_elem) * 2) ^ ((row & 7) << 4));
 }
 
+// two floats to one word of two bf16 (a low, b high), round-to-nearest-even:
+// as a 2-vector conversion this is ONE v_cvt_pk_bf16_f32; two scalar
+// conversions joined by shift and or cost four instructions for the same bits
+// (used by every t12_convert caller: flash_attn*_v2.hip, paged_attn_append.hip)
+typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ unsigned pack_bf16(float a, float b) {
-    return (unsigned)f32_to_bf16(a) | ((unsigned)f32_to_bf16(b) << 16);
+    union { bf16x2v h; unsigned u; } r;
+    r.h = __builtin_convertvector(f32x2{a, b}, bf16x2v);
+    return r.u;
 }
 
 // T12: convert one 16-row slice (regs rb..rb+7 of a 32x32 C tile) into the
