@@ -678,6 +678,18 @@ std::vector<torch::Tensor> flashmask_attn_bwd(torch::Tensor dout, torch::Tensor 
 // ---------------------------------------------------------------------------
 // paged-KV inference ops
 // ---------------------------------------------------------------------------
+// 0 = bf16 cache, 1 = int8, 2 = int4 packed nibbles, from the cache dtype
+static int kv_cache_mode(const torch::Tensor& k_cache,
+                         const c10::optional<torch::Tensor>& k_scale,
+                         const c10::optional<torch::Tensor>& v_scale) {
+    int cache_mode = 0;
+    if (k_cache.scalar_type() == torch::kChar) cache_mode = 1;
+    else if (k_cache.scalar_type() == torch::kByte) cache_mode = 2;
+    TORCH_CHECK(cache_mode == 0 || (k_scale.has_value() && v_scale.has_value()),
+                "quantized KV cache needs k_scale/v_scale");
+    return cache_mode;
+}
+
 torch::Tensor paged_decode_attn(torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cache,
                                 torch::Tensor block_table, torch::Tensor seq_lens,
                                 c10::optional<torch::Tensor> k_scale,
@@ -687,11 +699,7 @@ torch::Tensor paged_decode_attn(torch::Tensor q, torch::Tensor k_cache, torch::T
     int B = q.size(0), Hq = q.size(1), D = q.size(2);
     int block_size = k_cache.size(1), Hk = k_cache.size(2);
     int max_blocks = block_table.size(1);
-    int cache_mode = 0;
-    if (k_cache.scalar_type() == torch::kChar) cache_mode = 1;
-    else if (k_cache.scalar_type() == torch::kByte) cache_mode = 2;
-    TORCH_CHECK(cache_mode == 0 || (k_scale.has_value() && v_scale.has_value()),
-                "quantized KV cache needs k_scale/v_scale");
+    const int cache_mode = kv_cache_mode(k_cache, k_scale, v_scale);
     TORCH_CHECK(cache_mode != 2 || (D == 128 && Hq / Hk <= 16),
                 "int4 KV cache requires head dim 128 and GQA group <= 16");
     auto out = torch::empty_like(q);
@@ -728,11 +736,7 @@ torch::Tensor paged_append_attn(torch::Tensor q, torch::Tensor k_cache, torch::T
     int B = q.size(0), T = q.size(1), Hq = q.size(2), D = q.size(3);
     int block_size = k_cache.size(1), Hk = k_cache.size(2);
     int max_blocks = block_table.size(1);
-    int cache_mode = 0;
-    if (k_cache.scalar_type() == torch::kChar) cache_mode = 1;
-    else if (k_cache.scalar_type() == torch::kByte) cache_mode = 2;
-    TORCH_CHECK(cache_mode == 0 || (k_scale.has_value() && v_scale.has_value()),
-                "quantized KV cache needs k_scale/v_scale");
+    const int cache_mode = kv_cache_mode(k_cache, k_scale, v_scale);
     TORCH_CHECK(block_table.size(0) == B && seq_lens_before.numel() == B,
                 "block_table / seq_lens_before must have one row per sequence");
     TORCH_CHECK(!token_counts.has_value() || token_counts->numel() == B,
@@ -774,9 +778,7 @@ torch::Tensor rope_cache_append(torch::Tensor qkv, torch::Tensor k_cache, torch:
     CHECK_GPU(qkv); CHECK_CONTIG(qkv); CHECK_BF16(qkv);
     TORCH_CHECK(qkv.dim() == 3, "qkv must be [B, T, (Hq+2Hk)*D]");
     int B = qkv.size(0), T = qkv.size(1);
-    int cache_mode = 0;
-    if (k_cache.scalar_type() == torch::kChar) cache_mode = 1;
-    else if (k_cache.scalar_type() == torch::kByte) cache_mode = 2;
+    const int cache_mode = kv_cache_mode(k_cache, k_scale, v_scale);
     int D = (int)k_cache.size(3) * (cache_mode == 2 ? 2 : 1);
     int block_size = k_cache.size(1);
     int max_blocks = block_table.size(1);
@@ -787,8 +789,6 @@ torch::Tensor rope_cache_append(torch::Tensor qkv, torch::Tensor k_cache, torch:
     auto sf = sin_t.to(torch::kFloat32).contiguous();
     const int* tc = nullptr;
     if (token_counts.has_value()) tc = token_counts->data_ptr<int>();
-    TORCH_CHECK(cache_mode == 0 || (k_scale.has_value() && v_scale.has_value()),
-                "quantized KV cache needs k_scale/v_scale");
     TORCH_CHECK(cache_mode != 2 || D == 128, "int4 KV cache requires head dim 128");
     launch_rope_cache_append(qkv.data_ptr(), q_out.data_ptr(),
                              k_cache.data_ptr(), v_cache.data_ptr(),

@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 
 // A head dim without a compiled kernel is an error, never a silent no-op.
 [[noreturn]] inline void unsupported_head_dim(const char* op, int D) {
@@ -145,7 +146,18 @@ bool launch_flash_bwd2_mask(const void* dout, const void* q, const void* k,
                             float scale, hipStream_t stream,
                             const FlashStrides* strides = nullptr);
 
-// ---- paged_attn.hip / paged_attn_v2.hip ----
+// ---- paged-KV inference.  cache_mode: 0 = bf16 cache, 1 = int8, 2 = int4
+// packed nibbles; the kernels take it as a template argument. ----
+// f(std::integral_constant<int, cache_mode>{})
+template <class F>
+inline void dispatch_cache_mode(int cache_mode, F&& f) {
+    if (cache_mode == 2) f(std::integral_constant<int, 2>{});
+    else if (cache_mode == 1) f(std::integral_constant<int, 1>{});
+    else f(std::integral_constant<int, 0>{});
+}
+
+// ---- paged_attn.hip: decode entry point, scalar decode kernel, split fold,
+// rope + cache append ----
 int paged_decode_nsplit(int B, int Hk);
 void launch_paged_decode_attn(const void* q, const void* k_cache, const void* v_cache,
                               const float* k_scale, const float* v_scale,
@@ -154,6 +166,15 @@ void launch_paged_decode_attn(const void* q, const void* k_cache, const void* v_
                               int B, int Hq, int Hk, int D, int block_size,
                               int max_blocks, float scale, int cache_mode,
                               hipStream_t stream);
+void launch_rope_cache_append(const void* qkv, void* q_out, void* k_cache, void* v_cache,
+                              float* k_scale, float* v_scale,
+                              const int* block_table, const int* seq_lens_before,
+                              const float* cos_t, const float* sin_t,
+                              int B, int T, int Hq, int Hk, int D, int block_size,
+                              int max_blocks, const int* token_counts,
+                              int cache_mode, hipStream_t stream);
+
+// ---- paged_attn_mfma.hip: the MFMA tile loop behind decode and append ----
 // MFMA decode kernel; false (nothing launched) unless D==128 and G<=16.
 // Writes out (nsplit == 1) or the partials the split-merge kernel consumes.
 bool launch_paged_decode_attn3(const void* q, const void* k_cache, const void* v_cache,
@@ -163,17 +184,9 @@ bool launch_paged_decode_attn3(const void* q, const void* k_cache, const void* v
                                int B, int Hq, int Hk, int D, int block_size,
                                int max_blocks, float scale, int cache_mode,
                                hipStream_t stream);
-void launch_rope_cache_append(const void* qkv, void* q_out, void* k_cache, void* v_cache,
-                              float* k_scale, float* v_scale,
-                              const int* block_table, const int* seq_lens_before,
-                              const float* cos_t, const float* sin_t,
-                              int B, int T, int Hq, int Hk, int D, int block_size,
-                              int max_blocks, const int* token_counts,
-                              int cache_mode, hipStream_t stream);
-
-// ---- paged_attn_append.hip: T new tokens per sequence over the cache that
-// already holds them.  q/out are [B, T, Hq, D]; query token t of sequence b
-// sits at seq_lens_before[b] + t and attends to positions 0..that. ----
+// Append: T new tokens per sequence over the cache that already holds them.
+// q/out are [B, T, Hq, D]; query token t of sequence b sits at
+// seq_lens_before[b] + t and attends to positions 0..that.
 // Launch geometry: R = 1 or 2 16-row query tiles per workgroup (r_tiles = 0
 // picks it from the shape), row groups per (b, kv-head) and kv splits.  false
 // when the kernel does not take the shape (D != 128 or GQA group > 16).

@@ -91,7 +91,7 @@ __device__ __forceinline__ char* swz(ushort_t* base, int row, int col_elem) {
 // two floats to one word of two bf16 (a low, b high), round-to-nearest-even:
 // as a 2-vector conversion this is ONE v_cvt_pk_bf16_f32; two scalar
 // conversions joined by shift and or cost four instructions for the same bits
-// (used by every t12_convert caller: flash_attn*_v2.hip, paged_attn_append.hip)
+// (used by every t12_convert caller: flash_attn*_v2.hip, and by paged_attn_mfma.hip)
 typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ unsigned pack_bf16(float a, float b) {
     union { bf16x2v h; unsigned u; } r;

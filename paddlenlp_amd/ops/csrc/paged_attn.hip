@@ -9,8 +9,8 @@
 // loads and fp32 online-softmax state in registers.
 //
 // Cache layout: [num_blocks, block_size, Hk, D] bf16 per layer.
-#include "common.h"
 #include "launchers.h"
+#include "paged_kv.h"
 
 #define PA_WAVES 4
 #define PA_BLOCK (PA_WAVES * 64)
@@ -249,34 +249,13 @@ __global__ void paged_decode_merge_kernel(
     const int hk = blockIdx.y;
     const int g = blockIdx.z;
     const int G = Hq / Hk;
-    const int lane = threadIdx.x & 63;
-    constexpr int EPL = D / 64;
     const int seq_len = seq_lens[b];
     const int chunk = (seq_len + nsplit - 1) / nsplit;
     const float* base = partials +
         (((long long)b * Hk + hk) * nsplit) * (long long)G * (2 + D)
         + (long long)g * (2 + D);
-    float gm = -INFINITY;
-    for (int sp = 0; sp < nsplit; sp++) {
-        if (sp * chunk >= seq_len) break;
-        gm = fmaxf(gm, base[(long long)sp * G * (2 + D)]);
-    }
-    float gl = 0.f;
-    float oacc[EPL] = {0.f};
-    for (int sp = 0; sp < nsplit; sp++) {
-        if (sp * chunk >= seq_len) break;
-        const float* pp = base + (long long)sp * G * (2 + D);
-        float a = (pp[0] == -INFINITY) ? 0.f : __expf(pp[0] - gm);
-        gl += pp[1] * a;
-#pragma unroll
-        for (int e = 0; e < EPL; e++)
-            oacc[e] += pp[2 + lane * EPL + e] * a;
-    }
-    float inv = (gl > 0.f) ? 1.0f / gl : 0.f;
-    ushort_t* op = out + ((long long)b * Hq + hk * G + g) * D;
-#pragma unroll
-    for (int e = 0; e < EPL; e++)
-        op[lane * EPL + e] = f32_to_bf16(oacc[e] * inv);
+    pkv_fold_splits<D>(base, (long long)G * (2 + D), nsplit, chunk, seq_len,
+                       out + ((long long)b * Hq + hk * G + g) * D);
 }
 
 // ---------------------------------------------------------------------------
@@ -477,7 +456,7 @@ void launch_paged_decode_attn(const void* q, const void* k_cache, const void* v_
                               int max_blocks, float scale, int cache_mode,
                               hipStream_t stream) {
     if (D != 128 && D != 64) unsupported_head_dim("paged decode attention", D);
-    // main kernel: the MFMA kernel (paged_attn_v2.hip) when it accepts the
+    // main kernel: the MFMA kernel (paged_attn_mfma.hip) when it accepts the
     // shape, otherwise the scalar v1 kernel
     if (!launch_paged_decode_attn3(q, k_cache, v_cache, k_scale, v_scale,
                                    block_table, seq_lens, out, partials, nsplit,

@@ -1,6 +1,7 @@
-// Paged-KV cache access shared by the MFMA decode kernel (paged_attn_v2.hip)
-// and the multi-token append kernel (paged_attn_append.hip): workgroup
-// geometry, cache record addressing and the per-mode dequantising loads.
+// Paged-KV cache access of the MFMA decode and append kernels
+// (paged_attn_mfma.hip): workgroup geometry, cache record addressing and the
+// per-mode dequantising loads; and the fold of per-split partials that every
+// paged attention kernel's split path ends in.
 //
 // Cache layout: [num_blocks, block_size, Hk, D] per layer; MODE 0 = bf16,
 // 1 = int8, 2 = int4 packed nibbles (offset-binary q+8); quantised modes
@@ -105,4 +106,37 @@ __device__ __forceinline__ void pkv_write_vt(ushort_t* vt_lds, const short8v (&v
                 swz<PD3_TILE>(vt_lds, s_c + cc * 8 + j, s_r0)) = p32;
         }
     }
+}
+
+// Fold the fp32 partials {m, l, acc[D]} of one query row, one record per kv
+// split split_stride floats apart from base, into the bf16 row out_row: one
+// wave per row, lane takes D/64 columns.  Split sp covers positions
+// sp*chunk .. of kv_end; the splits past kv_end wrote nothing.
+template <int D>
+__device__ __forceinline__ void pkv_fold_splits(const float* __restrict__ base,
+                                                long long split_stride, int nsplit,
+                                                int chunk, int kv_end,
+                                                ushort_t* __restrict__ out_row) {
+    constexpr int EPL = D / 64;
+    const int lane = threadIdx.x & 63;
+    float gm = -INFINITY;
+    for (int sp = 0; sp < nsplit; sp++) {
+        if (sp * chunk >= kv_end) break;
+        gm = fmaxf(gm, base[sp * split_stride]);
+    }
+    float gl = 0.f;
+    float oacc[EPL] = {0.f};
+    for (int sp = 0; sp < nsplit; sp++) {
+        if (sp * chunk >= kv_end) break;
+        const float* pp = base + sp * split_stride;
+        float a = (pp[0] == -INFINITY) ? 0.f : __expf(pp[0] - gm);
+        gl += pp[1] * a;
+#pragma unroll
+        for (int e = 0; e < EPL; e++)
+            oacc[e] += pp[2 + lane * EPL + e] * a;
+    }
+    float inv = (gl > 0.f) ? 1.0f / gl : 0.f;
+#pragma unroll
+    for (int e = 0; e < EPL; e++)
+        out_row[lane * EPL + e] = f32_to_bf16(oacc[e] * inv);
 }
