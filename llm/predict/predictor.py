@@ -345,7 +345,9 @@ def create_predictor(predictor_args: PredictorArgument, model=None, tokenizer=No
         if torch.cuda.is_available():
             model = model.to("cuda:0")
     if predictor_args.inference_model and predictor_args.block_attn:
-        engine = FusedMultiTransformer.from_llama(
+        # from_model dispatches on the family (Llama, Qwen2, Mixtral); on a
+        # Mixtral, quant_type "weight_only_int8" reaches the experts too
+        engine = FusedMultiTransformer.from_model(
             model, block_size=predictor_args.block_size,
             max_seq_len=predictor_args.total_max_length)
         if predictor_args.quant_type:

@@ -196,7 +196,8 @@ class FusedMultiTransformer(nn.Module):
     v_scales = None
     tp_group = None  # set by from_llama(tp_degree > 1): row-parallel reduce
     # Routed FFN: "auto" takes the fused sync-free kernels (ops.moe_ffn) for
-    # GPU inputs they support, up to moe_fused_max_tokens tokens; "torch"
+    # GPU inputs they support, up to moe_fused_max_tokens tokens
+    # (ops.moe_ffn_wint8 once the experts are quantized to int8); "torch"
     # always runs the capacity-padded torch formulation.
     moe_impl: str = "auto"
     # Measured (tools/bench_moe.py, profiles/moe_ffn.md, one Mixtral-8x7B
@@ -420,15 +421,38 @@ class FusedMultiTransformer(nn.Module):
         `names` restricts quantization, e.g. the bandwidth-bound subset
         ("gate_up_weights", "down_weights", "lm_head") — at decode batch
         sizes the skinny qkv/o GEMMs are latency-bound and fp8 does not
-        pay there (see profiles/r02_decode_throughput.md)."""
-        from ..quantization import quantize_fp8, quantize_int8
+        pay there (see profiles/r02_decode_throughput.md).
+
+        On a MoE engine "moe_experts" stands for the stacked expert weights
+        (moe_w1, moe_w3, moe_w2; about 96 % of a Mixtral's bytes).  With
+        algo="weight_only_int8" it is part of the default set: the experts
+        are packed per layer with quantize_moe_int8 (int8, one fp32 scale per
+        expert and output column) and the decode path streams the int8 bytes
+        (ops.moe_ffn_wint8).  algo="fp8" leaves the experts in the compute
+        dtype, as before: the fp8 MFMA wants quantized activations too, which
+        is another numerical contract.  The router weights (moe_gates) are
+        never quantized."""
+        from ..quantization import quantize_fp8, quantize_int8, quantize_moe_int8
 
         qfn = quantize_fp8 if algo == "fp8" else quantize_int8
         self._qw = {}
         all_names = ("qkv_weights", "out_proj_weights", "gate_up_weights",
                      "down_weights")
+        if algo == "weight_only_int8" and self.config.moe_num_experts > 0:
+            all_names += ("moe_experts",)
         names = tuple(names) if names is not None else all_names
         for name in names:
+            if name == "moe_experts":
+                if algo != "weight_only_int8" or self.config.moe_num_experts <= 0:
+                    raise ValueError(
+                        "moe_experts: only weight_only_int8 on a MoE engine is supported")
+                for wname in ("moe_w1", "moe_w3", "moe_w2"):
+                    qs = []
+                    for w in getattr(self, wname):
+                        qs.append(quantize_moe_int8(w.data))
+                        w.data = w.data.new_zeros(1)  # free the bf16 copy
+                    self._qw[wname] = qs
+                continue
             if name == "lm_head":
                 q, sc = qfn(self.lm_head.data)
                 self._qw["lm_head"] = [(q, sc)]
@@ -457,7 +481,14 @@ class FusedMultiTransformer(nn.Module):
         """Routed MoE FFN (mixtral): top-k router + capacity-padded batched
         GEMMs over the stacked expert weights (same grouped-GEMM scheme as
         parallel.expert_parallel.GroupedExperts; reference fused_moe,
-        fused_transformer_layers.py:951-1008)."""
+        fused_transformer_layers.py:951-1008).
+
+        With int8 experts (quantize("weight_only_int8")) the fused path is
+        ops.moe_ffn_wint8 under the same conditions.  Every other case (CPU,
+        moe_impl="torch", more than moe_fused_max_tokens tokens, unsupported
+        shapes) dequantizes ALL of the layer's experts to the compute dtype
+        on every call and then runs the torch formulation: correct, but slow
+        and, for the time of the call, as large as the unquantized layer."""
         c = self.config
         shp = h.shape
         x = h.reshape(-1, shp[-1])
@@ -466,13 +497,25 @@ class FusedMultiTransformer(nn.Module):
         router = x @ self.moe_gates[i].t()
         if self.moe_impl not in ("auto", "torch"):
             raise ValueError(f"moe_impl must be 'auto' or 'torch', got {self.moe_impl!r}")
-        if (self.moe_impl == "auto" and x.is_cuda and T <= self.moe_fused_max_tokens
-                and ops.moe_ffn_supported(x, router, self.moe_w1[i], self.moe_w3[i],
-                                          self.moe_w2[i], K)):
-            # on-device routing + grouped GEMMs over the selected experts
-            # only; no host sync, so the decode step stays capturable
-            return ops.moe_ffn(x, router, self.moe_w1[i], self.moe_w3[i],
-                               self.moe_w2[i], K).reshape(shp)
+        fused_ok = (self.moe_impl == "auto" and x.is_cuda
+                    and T <= self.moe_fused_max_tokens)
+        if "moe_w1" in self._qw:
+            (q1, s1), (q3, s3), (q2, s2) = (
+                self._qw[n][i] for n in ("moe_w1", "moe_w3", "moe_w2"))
+            if fused_ok and ops.moe_ffn_wint8_supported(x, router, q1, s1, q3, s3,
+                                                        q2, s2, K):
+                return ops.moe_ffn_wint8(x, router, q1, s1, q3, s3, q2, s2,
+                                         K).reshape(shp)
+            from ..quantization import dequantize_moe_int8
+
+            w1, w3, w2 = (dequantize_moe_int8(q, s, x.dtype)
+                          for q, s in ((q1, s1), (q3, s3), (q2, s2)))
+        else:
+            w1, w3, w2 = self.moe_w1[i], self.moe_w3[i], self.moe_w2[i]
+            if fused_ok and ops.moe_ffn_supported(x, router, w1, w3, w2, K):
+                # on-device routing + grouped GEMMs over the selected experts
+                # only; no host sync, so the decode step stays capturable
+                return ops.moe_ffn(x, router, w1, w3, w2, K).reshape(shp)
         probs = router.float().softmax(-1)
         topw, tope = probs.topk(K, dim=-1)
         topw = (topw / topw.sum(-1, keepdim=True)).to(x.dtype)
@@ -491,10 +534,9 @@ class FusedMultiTransformer(nn.Module):
             idx = tok_e * C + pos
             xp = sorted_x.new_zeros(E * C, shp[-1]).index_copy(0, idx, sorted_x)
             xp = xp.view(E, C, shp[-1])
-            gu = torch.cat([torch.bmm(xp, self.moe_w1[i]),
-                            torch.bmm(xp, self.moe_w3[i])], dim=-1)
+            gu = torch.cat([torch.bmm(xp, w1), torch.bmm(xp, w3)], dim=-1)
             act = ops.swiglu(gu) if gu.is_cuda else reference.swiglu(gu)
-            yp = torch.bmm(act, self.moe_w2[i])
+            yp = torch.bmm(act, w2)
             out_sorted = yp.reshape(E * C, shp[-1]).index_select(0, idx)
         out_flat = torch.empty_like(out_sorted)
         out_flat[sort_idx] = out_sorted

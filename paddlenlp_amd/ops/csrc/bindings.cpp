@@ -953,6 +953,79 @@ torch::Tensor moe_ffn(torch::Tensor x, torch::Tensor router_logits, torch::Tenso
     return out;
 }
 
+// Weight-only int8 experts: q1/q3 [E, I, H], q2 [E, H, I] int8 with the
+// contraction dimension contiguous, s1/s3 [E, I], s2 [E, H] fp32.
+torch::Tensor moe_ffn_wint8(torch::Tensor x, torch::Tensor router_logits,
+                            torch::Tensor q1, torch::Tensor s1, torch::Tensor q3,
+                            torch::Tensor s3, torch::Tensor q2, torch::Tensor s2,
+                            int64_t top_k) {
+    CHECK_GPU(x); CHECK_CONTIG(x); CHECK_BF16(x);
+    CHECK_GPU(q1); CHECK_CONTIG(q1); CHECK_GPU(s1); CHECK_CONTIG(s1);
+    CHECK_GPU(q3); CHECK_CONTIG(q3); CHECK_GPU(s3); CHECK_CONTIG(s3);
+    CHECK_GPU(q2); CHECK_CONTIG(q2); CHECK_GPU(s2); CHECK_CONTIG(s2);
+    TORCH_CHECK(q1.scalar_type() == torch::kInt8 && q3.scalar_type() == torch::kInt8 &&
+                q2.scalar_type() == torch::kInt8, "moe_ffn_wint8: q1/q3/q2 must be int8");
+    TORCH_CHECK(s1.scalar_type() == torch::kFloat32 && s3.scalar_type() == torch::kFloat32 &&
+                s2.scalar_type() == torch::kFloat32, "moe_ffn_wint8: s1/s3/s2 must be fp32");
+    check_moe_route_args(router_logits, top_k);
+    TORCH_CHECK(x.dim() == 2 && q1.dim() == 3 && q3.dim() == 3 && q2.dim() == 3 &&
+                s1.dim() == 2 && s3.dim() == 2 && s2.dim() == 2,
+                "moe_ffn_wint8: x [T, H], q1/q3 [E, I, H], q2 [E, H, I], "
+                "s1/s3 [E, I], s2 [E, H]");
+    const int T = x.size(0), H = x.size(1);
+    const int E = q1.size(0), I = q1.size(1), K = (int)top_k;
+    TORCH_CHECK(router_logits.size(0) == T && router_logits.size(1) == E,
+                "moe_ffn_wint8: router logits must be [T, E]");
+    TORCH_CHECK(q1.size(2) == H && q3.sizes() == q1.sizes() && q2.size(0) == E &&
+                q2.size(1) == H && q2.size(2) == I,
+                "moe_ffn_wint8: q1/q3 [E, I, H], q2 [E, H, I]");
+    TORCH_CHECK(s1.size(0) == E && s1.size(1) == I && s3.sizes() == s1.sizes() &&
+                s2.size(0) == E && s2.size(1) == H,
+                "moe_ffn_wint8: s1/s3 [E, I], s2 [E, H]");
+    TORCH_CHECK(H % 128 == 0 && I % 128 == 0,
+                "moe_ffn_wint8: H and I must be multiples of 128");
+    TORCH_CHECK((long)T * K <= kMoeMaxFlatRows, "moe_ffn_wint8: T * top_k must be <= ",
+                kMoeMaxFlatRows);
+    // LDS-DMA sources: 16-byte aligned bases (rows are multiples of 128 bytes)
+    TORCH_CHECK(aligned16(x) && aligned16(q1) && aligned16(q3) && aligned16(q2),
+                "moe_ffn_wint8: x and the weights must be 16-byte aligned");
+    auto out = torch::empty({(long)T, (long)H}, x.options());
+    if (T == 0) return out;
+
+    auto stream = cur_stream();
+    auto i32 = x.options().dtype(torch::kInt32);
+    auto f32 = x.options().dtype(torch::kFloat32);
+    const long P = moe_padded_rows(T, K, E);
+    const int ks = moe_down_ksplit_wint8(T, K, H, I);
+    auto ids = torch::empty({(long)T, (long)K}, i32);
+    auto topw = torch::empty({(long)T, (long)K}, f32);
+    auto sorted_rows = torch::empty({P}, i32);
+    auto tile_expert = torch::empty({P / kMoeRowTile}, i32);
+    auto row_pos = torch::empty({(long)T, (long)K}, i32);
+    auto num_tiles = torch::empty({1}, i32);
+    auto zero_row = torch::zeros({(long)H}, x.options());
+    auto act = torch::empty({P, (long)I}, x.options());
+    auto partial = torch::empty({(long)ks, P, (long)H}, f32);
+
+    launch_moe_route(router_logits.data_ptr(),
+                     router_logits.scalar_type() == torch::kBFloat16,
+                     ids.data_ptr<int>(), topw.data_ptr<float>(), T, E, K, stream);
+    launch_moe_align(ids.data_ptr<int>(), sorted_rows.data_ptr<int>(),
+                     tile_expert.data_ptr<int>(), row_pos.data_ptr<int>(),
+                     num_tiles.data_ptr<int>(), T, K, E, stream);
+    launch_moe_gate_up_wint8(x.data_ptr(), zero_row.data_ptr(), q1.data_ptr(),
+                             s1.data_ptr<float>(), q3.data_ptr(), s3.data_ptr<float>(),
+                             sorted_rows.data_ptr<int>(), tile_expert.data_ptr<int>(),
+                             num_tiles.data_ptr<int>(), act.data_ptr(), T, K, E, H, I,
+                             stream);
+    launch_moe_down_wint8(act.data_ptr(), q2.data_ptr(), s2.data_ptr<float>(),
+                          tile_expert.data_ptr<int>(), num_tiles.data_ptr<int>(),
+                          partial.data_ptr<float>(), ks, T, K, E, H, I, stream);
+    launch_moe_combine(partial.data_ptr<float>(), row_pos.data_ptr<int>(),
+                       topw.data_ptr<float>(), out.data_ptr(), ks, T, K, E, H, stream);
+    return out;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("rms_norm_fwd", &rms_norm_fwd);
     m.def("rms_norm_bwd", &rms_norm_bwd);
@@ -1017,4 +1090,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("moe_ffn", &moe_ffn, py::arg("x"), py::arg("router_logits"),
           py::arg("w1"), py::arg("w3"), py::arg("w2"), py::arg("top_k"));
     m.def("moe_down_ksplit", &moe_down_ksplit);
+    m.def("moe_ffn_wint8", &moe_ffn_wint8, py::arg("x"), py::arg("router_logits"),
+          py::arg("q1"), py::arg("s1"), py::arg("q3"), py::arg("s3"),
+          py::arg("q2"), py::arg("s2"), py::arg("top_k"));
+    m.def("moe_down_ksplit_wint8", &moe_down_ksplit_wint8);
 }

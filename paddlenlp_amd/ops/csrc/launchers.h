@@ -246,6 +246,20 @@ void launch_moe_down(const void* act_sorted, const void* w2,
 void launch_moe_combine(const float* partial, const int* row_pos,
                         const float* topk_w, void* out, int ksplit, int T,
                         int K, int E, int H, hipStream_t stream);
+// Weight-only int8 experts: q1/q3 [E, I, H], q2 [E, H, I] int8 (contraction
+// contiguous), s1/s3 [E, I], s2 [E, H] fp32 per-column scales.  Route, align
+// and combine are the launches above; the down split is counted in this
+// path's own 128-deep chunks (moe_down_ksplit_wint8).
+int moe_down_ksplit_wint8(int T, int K, int H, int I);
+void launch_moe_gate_up_wint8(const void* x, const void* zero_row, const void* q1,
+                              const float* s1, const void* q3, const float* s3,
+                              const int* sorted_rows, const int* tile_expert,
+                              const int* num_tiles, void* act_sorted, int T, int K,
+                              int E, int H, int I, hipStream_t stream);
+void launch_moe_down_wint8(const void* act_sorted, const void* q2, const float* s2,
+                           const int* tile_expert, const int* num_tiles,
+                           float* partial, int ksplit, int T, int K, int E, int H,
+                           int I, hipStream_t stream);
 
 // ---- sampling.hip ----
 void launch_repetition_penalty(void* logits, const long long* pre_ids,

@@ -450,3 +450,54 @@ def moe_ffn(x: torch.Tensor, router_logits: torch.Tensor, w1: torch.Tensor,
             xc = xc.clone()
         return C.moe_ffn(xc, router_logits.contiguous(), w1, w3, w2, top_k)
     return reference.moe_ffn(x, router_logits, w1, w3, w2, top_k).to(x.dtype)
+
+
+def moe_ffn_wint8_supported(x: torch.Tensor, router_logits: torch.Tensor,
+                            q1: torch.Tensor, s1: torch.Tensor, q3: torch.Tensor,
+                            s3: torch.Tensor, q2: torch.Tensor, s2: torch.Tensor,
+                            top_k: int) -> bool:
+    """True when the fused int8-weight kernels take these arguments: bf16 x on
+    the GPU, contiguous int8 q1/q3 [E, I, H] and q2 [E, H, I] with 16-byte
+    aligned bases, contiguous fp32 scales s1/s3 [E, I] and s2 [E, H], H and I
+    multiples of 128, E <= 64, top_k <= 8, T * top_k <= 4096."""
+    if not (x.is_cuda and x.dim() == 2 and q1.dim() == 3 and q2.dim() == 3):
+        return False
+    T, H = x.shape
+    E, I, _ = q1.shape
+    if not _moe_route_supported(router_logits, top_k):
+        return False
+    if tuple(router_logits.shape) != (T, E) or T * top_k > MOE_MAX_FLAT_ROWS:
+        return False
+    if H % 128 or I % 128 or x.dtype != torch.bfloat16:
+        return False
+    if q1.shape != (E, I, H) or q3.shape != (E, I, H) or q2.shape != (E, H, I):
+        return False
+    if s1.shape != (E, I) or s3.shape != (E, I) or s2.shape != (E, H):
+        return False
+    for q in (q1, q3, q2):
+        if (q.dtype != torch.int8 or not q.is_cuda or not q.is_contiguous()
+                or q.data_ptr() % 16):
+            return False
+    for s in (s1, s3, s2):
+        if s.dtype != torch.float32 or not s.is_cuda or not s.is_contiguous():
+            return False
+    return True
+
+
+def moe_ffn_wint8(x: torch.Tensor, router_logits: torch.Tensor, q1: torch.Tensor,
+                  s1: torch.Tensor, q3: torch.Tensor, s3: torch.Tensor,
+                  q2: torch.Tensor, s2: torch.Tensor, top_k: int) -> torch.Tensor:
+    """moe_ffn over weight-only int8 experts in the layout of
+    quantization.quantize_moe_int8 (q1/q3 [E, I, H], q2 [E, H, I] int8, one
+    fp32 scale per expert and output column); x [T, H] -> [T, H] in x.dtype.
+    The kernels stream the int8 bytes of the selected experts only, convert
+    them to bf16 in registers (exactly) and apply the scale to the fp32 sums."""
+    if moe_ffn_wint8_supported(x, router_logits, q1, s1, q3, s3, q2, s2, top_k):
+        C = _load_extension()
+        xc = x.contiguous()
+        if xc.data_ptr() % 16:
+            xc = xc.clone()
+        return C.moe_ffn_wint8(xc, router_logits.contiguous(), q1, s1, q3, s3, q2, s2,
+                               top_k)
+    return reference.moe_ffn_wint8(x, router_logits, q1, s1, q3, s3, q2, s2,
+                                   top_k).to(x.dtype)

@@ -118,6 +118,32 @@ def moe_ffn(x: torch.Tensor, router_logits: torch.Tensor, w1: torch.Tensor,
     return out
 
 
+def moe_ffn_wint8(x: torch.Tensor, router_logits: torch.Tensor,
+                  q1: torch.Tensor, s1: torch.Tensor, q3: torch.Tensor, s3: torch.Tensor,
+                  q2: torch.Tensor, s2: torch.Tensor, top_k: int) -> torch.Tensor:
+    """moe_ffn over weight-only int8 experts as quantization.quantize_moe_int8
+    packs them: q1/q3 [E, I, H], q2 [E, H, I] int8 (contraction contiguous),
+    s1/s3 [E, I], s2 [E, H] fp32.  The weights are dequantized to fp32
+    (q * scale, then the layout of moe_ffn) and handed to moe_ffn; returns fp32
+    [T, H].
+
+    Only the selected experts are dequantized, the others stay zero and are
+    never visited, so an unselected expert may hold anything (NaN scales
+    included)."""
+    from ..quantization import dequantize_moe_int8
+
+    ids, _ = moe_route(router_logits, top_k)
+    sel = torch.unique(ids).long()
+
+    def deq(q, s):
+        w = torch.zeros(q.shape[0], q.shape[2], q.shape[1], dtype=torch.float32,
+                        device=q.device)
+        w[sel] = dequantize_moe_int8(q[sel], s[sel], torch.float32)
+        return w
+
+    return moe_ffn(x, router_logits, deq(q1, s1), deq(q3, s3), deq(q2, s2), top_k)
+
+
 def flash_attention(
     q: torch.Tensor,  # [B, S, Hq, D]
     k: torch.Tensor,  # [B, S, Hk, D]

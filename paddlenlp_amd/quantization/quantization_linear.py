@@ -28,6 +28,26 @@ def quantize_int8(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     return q, scale
 
 
+def quantize_moe_int8(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Stacked expert weights w [E, Kd, N] (the engine's layout, N contiguous)
+    -> (q [E, N, Kd] int8, scale [E, N] fp32): symmetric int8 per (expert,
+    output column) by the rules of quantize_int8.  The packed tensor is
+    contraction-major (Kd contiguous): the 8 int8 values one lane feeds to an
+    MFMA are then 8 consecutive bytes of a column (moe_ffn.hip)."""
+    assert w.dim() == 3, w.shape
+    wt = w.transpose(1, 2)                                   # [E, N, Kd] view
+    scale = wt.abs().amax(dim=2).clamp(min=1e-8).float() / 127.0
+    q = torch.clamp(torch.round(wt.float() / scale[:, :, None]), -127, 127)
+    return q.to(torch.int8).contiguous(), scale
+
+
+def dequantize_moe_int8(q: torch.Tensor, scale: torch.Tensor,
+                        dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """(q [E, N, Kd] int8, scale [E, N]) -> w [E, Kd, N] in dtype: the
+    inverse layout change of quantize_moe_int8, q * scale in fp32."""
+    return (q.float() * scale.float()[:, :, None]).to(dtype).transpose(1, 2).contiguous()
+
+
 def quantize_int4(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """Per-output-channel symmetric int4: w [out, in] -> (packed uint8
     [out, in//2] with two nibbles per byte, fp32 scale[out])."""
